@@ -9,7 +9,19 @@ GPU checksums its own 256 MiB batch, no data-path collective).  The batch
 rotates over NBUF distinct 256 MiB buffers so consecutive steps cannot be
 served from the 256 MiB Infinity Cache.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, settles, warms up, times the K steps and prints the
+line: value, ms_per_step and the roofline fields come from those K steps
+alone, and every field that takes a run or a check of its own is null.
+--full adds those after the timed steps: the bit-exact checks against the
+reference, the host-issued comparison, read-side verification, the read
+probe, the host-resident runs, the gather at N > 1, the config4 and
+strong_scaling sub-objects and the CPU baseline; everything below about
+them holds under --full.  --dump-outputs DIR writes the checksum array the
+last timed step produced to DIR/checksums.npy (float64, exact for 32-bit
+values); the inputs depend on the arguments alone, so two builds can be
+compared output for output.
 
 N > 1 runs one rank per GPU.  Launched by torch.distributed.run (WORLD_SIZE
 set, as the driver does) every process is one rank; launched plainly with
@@ -20,7 +32,7 @@ arrays are gathered to rank 0 over RCCL (the only collective of configs 2/5;
 timed separately as "gather_ms"; config 4 gathers inside every step).
 Rank 0 prints ONE JSON line.
 
-The default line (config 2, weak scaling) also carries, at every N, the two
+With --full the default line (config 2, weak scaling) also carries, at every N, the two
 other shapes BASELINE.json's 1/2/4/8-GPU curve is quoted on (each timed like
 the main steps: K steps, graph-replayed, max over ranks, bit-exact against
 the reference):
@@ -91,6 +103,23 @@ def reference_checksums(payload: np.ndarray, pk, nout: int) -> np.ndarray:
     out = np.zeros(max(nout, 1), np.uint32)
     impl.batch_mt_seconds(payload, pk, out, max(1, min(16, os.cpu_count() or 1)), 1)
     return out[:nout]
+
+
+DUMP_MAX_VALUES = 4 << 20  # --dump-outputs: at most 32 MiB of float64 per array
+
+
+def dump_outputs(dirname: str, rank: int, checksums: np.ndarray) -> None:
+    """--dump-outputs: the checksum array of the last timed step as
+    DIR/checksums.npy (rank r > 0: checksums_rank<r>.npy), float64 (exact for
+    32-bit values).  An array of more than DUMP_MAX_VALUES checksums is cut to
+    a fixed sample of that many (seeded indices, ascending, the same in every
+    run)."""
+    a = np.ascontiguousarray(checksums).view(np.uint32)
+    if a.size > DUMP_MAX_VALUES:
+        a = a[np.sort(np.random.default_rng(20240).integers(0, a.size, DUMP_MAX_VALUES))]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "checksums.npy" if rank == 0 else "checksums_rank%d.npy" % rank),
+            a.astype(np.float64))
 
 
 def baseline_metric() -> str:
@@ -697,8 +726,9 @@ def run_config4(hdfs, args, env) -> dict:
     step(0)
     join(sptr)
     torch.cuda.synchronize()
-    want0 = reference_checksums(file0, file_pk, nchk) if rank == 0 else None
-    gate = rank != 0 or bool(np.array_equal(root_outs[0].cpu().numpy().view(np.uint32)[:nchk], want0))
+    full = args.full  # (without --full: the timed steps alone, no check, no sub-timing)
+    want0 = reference_checksums(file0, file_pk, nchk) if rank == 0 and full else None
+    gate = rank != 0 or not full or bool(np.array_equal(root_outs[0].cpu().numpy().view(np.uint32)[:nchk], want0))
 
     def zero_roots():
         for o in root_outs:
@@ -707,11 +737,13 @@ def run_config4(hdfs, args, env) -> dict:
     r = time_steps(env, args, step, warm_step, collective=world > 1, use_graph=not (args.no_graph or rehearsal),
                    zero=zero_roots, probe=probe, on_abandon=abandon, settle_ms=0 if rehearsal else None,
                    finish=join, host_lead=False)
+    if args.dump_outputs and args.config == "c4" and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, 0, root_outs[(args.steps - 1) % nbuf].cpu().numpy()[:nchk])
     # every file the timed steps gathered, against the reference (rank 0;
     # root_outs[b] holds the last timed step on buffer b)
     timed = True
     timed_bufs = sorted({i % nbuf for i in range(args.steps)})
-    if rank == 0:
+    if rank == 0 and full:
         for b in timed_bufs:
             wb = want0 if b == 0 else reference_checksums(synthetic_bytes(file_bytes_total, 2024 + b), file_pk, nchk)
             timed = timed and bool(np.array_equal(root_outs[b].cpu().numpy().view(np.uint32)[:nchk], wb))
@@ -720,7 +752,7 @@ def run_config4(hdfs, args, env) -> dict:
     # (every rank or none: the timing holds collectives)
     shard_max = None
     rs = None
-    if not rehearsal and agree_min(env, splan is not None):
+    if full and not rehearsal and agree_min(env, splan is not None):
         def sstep(i, sp=None):
             splan.exec(bufs[i % nbuf].data_ptr(), local_out.data_ptr(), sptr if sp is None else sp)
         rs = time_steps(env, args, sstep, sstep, use_graph=r["use_graph"], settle_ms=min(args.settle_ms, 50.0))
@@ -729,7 +761,7 @@ def run_config4(hdfs, args, env) -> dict:
     # right after (a 20-step window of 24-us steps holds a few us of window
     # effects: 25.2 against 24.2 us on one box, round 5).
     steady = None
-    if not rehearsal and args.steps < 500:
+    if full and not rehearsal and args.steps < 500:
         import copy
 
         a500 = copy.copy(args)
@@ -738,7 +770,7 @@ def run_config4(hdfs, args, env) -> dict:
                          zero=zero_roots, settle_ms=0, finish=join, host_lead=False)
         steady = rst["kernel_ms"] * 1e3
         rst["graphs"].clear()
-    exact = agree_min(env, gate and timed)
+    exact = agree_min(env, gate and timed) if full else None
     launch = launch_text(r)
     # the step graphs hold the RCCL group's captured calls: destroyed before
     # the communicator
@@ -777,7 +809,8 @@ def run_config4(hdfs, args, env) -> dict:
         "gather_ops": None if gops is None else gops[0], "gather_packed": None if gops is None else gops[1],
         "bit_exact": exact,
         "bit_exact_checks": {"before_warmup_file0": gate,
-                             "timed_files_buf%s" % "_".join(str(b) for b in timed_bufs): timed} if rank == 0 else None,
+                             "timed_files_buf%s" % "_".join(str(b) for b in timed_bufs): timed}
+        if rank == 0 and full else None,
         "pipelined": pipeline,
         "launch": launch, "lead_steps": "host-issued" if (r["lead_host"] or not r["use_graph"]) else "graph",
         "host_issue_us_per_step": round(r["host_issue_us"], 2),
@@ -856,6 +889,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=500)
     ap.add_argument("--config", default="c2", type=config_name,
                     help="c2 | c3 | c4 | c5 | c2b1536 | c2b1000 | c2b<bpc> | c2u | c2t | c3u")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the bit-exact "
+                         "checks against the reference, the host-issued comparison, read-side verification, the read "
+                         "probe, the host-resident runs, the gather at N > 1, the config4 and strong_scaling sub-runs "
+                         "and the CPU baseline (--two-streams, --host-sweep, --no-cpu, --no-host, --no-config4 and "
+                         "--no-strong choose among these).  Without it the line carries the timed steps alone and "
+                         "the other fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the checksum array the last timed step produced to DIR/checksums.npy (float64, exact "
+                         "for 32-bit values; rank r > 0 writes checksums_rank<r>.npy).  Same arguments, same inputs: "
+                         "two builds can be compared output for output")
     ap.add_argument("--nbuf", type=int, default=4, help="rotating payload buffers (defeat the 256 MiB L3)")
     ap.add_argument("--cpu-seconds", type=float, default=4.0)
     ap.add_argument("--no-cpu", action="store_true")
@@ -884,6 +928,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if (args.two_streams or args.host_sweep) and not args.full:
+        ap.error("--two-streams and --host-sweep are measured under --full")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             sys.exit(launch_ranks(args))
@@ -949,9 +995,9 @@ def main():
                                   "algorithmic_bytes_per_launch": C4_BLOCKS * shard.BLOCK_BYTES,
                                   "shard_frac_per_gpu": c4["shard_frac_of_hbm_roofline"]},
                                  **roofline_node(C4_BLOCKS * shard.BLOCK_BYTES // world, kus, world)),
-                "cpu_baseline": None, "bit_exact_vs_reference": c4["bit_exact"], "config4": c4,
+                "cpu_baseline": None, "full": args.full, "bit_exact_vs_reference": c4["bit_exact"], "config4": c4,
             }
-        if not args.no_cpu:  # (rank 0, after every rank's GPU work; the others wait)
+        if args.full and not args.no_cpu:  # (rank 0, after every rank's GPU work; the others wait)
             from hdfs_crc32c_amd.workloads import uniform_packets
 
             cb = cpu_baseline_on_rank0(env, lambda: cpu_baseline(
@@ -999,10 +1045,13 @@ def main():
     # correctness gate (outside the timed region): every buffer-0 checksum
     step(0)
     torch.cuda.synchronize()
-    want = reference_checksums(payload0, pk, nout)
-    got0 = outs[0].cpu().numpy().view(np.uint32)[:nout]
-    bit_exact = bool(np.array_equal(got0, want))
-    gate_exact = bit_exact
+    want = None
+    bit_exact = gate_exact = True
+    if args.full:
+        want = reference_checksums(payload0, pk, nout)
+        got0 = outs[0].cpu().numpy().view(np.uint32)[:nout]
+        bit_exact = bool(np.array_equal(got0, want))
+        gate_exact = bit_exact
 
     # settle and warm-up steps write a scratch copy of the outputs (same
     # payloads, same plan), so the checks after the timed region see only
@@ -1020,13 +1069,15 @@ def main():
     r = time_steps(env, args, step, warm_step, use_graph=not args.no_graph, zero=zero_outs)
     elapsed, kernel_ms, window_ms = r["elapsed"], r["kernel_ms"], r["window_ms"]
     use_graph, graphs, parts = r["use_graph"], r["graphs"], r["parts"]
+    if args.dump_outputs and args.steps > 0:  # (before anything below writes the outputs again)
+        dump_outputs(args.dump_outputs, rank, outs[(args.steps - 1) % nbuf].cpu().numpy()[:nout])
 
     # Correctness of the timed launches themselves (outside the timed region):
     # the checksums the last timed launch on buffer 0 (PCG64 host bytes) and
     # on buffer 1 (device random bytes, copied back) wrote, against the
     # reference's crc32c.c.
     timed_checks = {}
-    if args.steps > 0:
+    if args.full and args.steps > 0:
         timed_checks["timed_buf0"] = bool(np.array_equal(outs[0].cpu().numpy().view(np.uint32)[:nout], want))
         if nbuf > 1 and args.steps > 1:
             w1 = reference_checksums(bufs[1].cpu().numpy(), pk, nout)
@@ -1034,7 +1085,7 @@ def main():
                 np.array_equal(outs[1].cpu().numpy().view(np.uint32)[:nout], w1))
     timed_exact = all(timed_checks.values())
     eager_ms = None
-    if use_graph:  # the same steps issued one by one from the host, for comparison
+    if args.full and use_graph:  # the same steps issued one by one from the host, for comparison
         # (after the checks above the GPU sat idle for a while: settle again,
         # or the host-issued launches ride the power transient)
         settle_for(env, args.settle_ms, warm_step, False)
@@ -1048,7 +1099,7 @@ def main():
         torch.cuda.synchronize()
         eager_ms = e0.elapsed_time(e1) / ne
 
-    if world > 1:
+    if args.full and world > 1:
         ok = torch.tensor([1 if bit_exact and timed_exact else 0], dtype=torch.int32, device=cdev)
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         bit_exact = bool(ok.item())
@@ -1056,7 +1107,7 @@ def main():
     # rank's checksum array to rank 0 after the timed region, timed on its
     # own.  (Config 4's gather is inside every step: the config4 sub-object.)
     gather_ms = None
-    if world > 1:
+    if args.full and world > 1:
         torch.cuda.synchronize()
         g0 = time.perf_counter()
         send = outs[0].to(cdev)
@@ -1073,7 +1124,7 @@ def main():
     # against their checksums (outs[b] now holds buffer b's), timed the same
     # way (rank 0, reported beside the main line).
     verify = None
-    if rank == 0:
+    if args.full and rank == 0:
         res = torch.zeros(2, dtype=torch.int32, device=dev)
         for i in range(200):
             plan.verify(bufs[i % nbuf].data_ptr(), outs[i % nbuf].data_ptr(), res.data_ptr(), sptr)
@@ -1146,7 +1197,7 @@ def main():
     # prices the kernel against what this chip actually streams, beside the
     # 8 TB/s datasheet peak.  Rank 0, N = 1 only.
     read_probe = None
-    if rank == 0 and world == 1 and nbuf > 1:
+    if args.full and rank == 0 and world == 1 and nbuf > 1:
         probe_out = torch.zeros(1 << 20, dtype=torch.int32, device=dev)
         L = hdfs.debug_lib()  # the read probe lives in the debug library, not the product
 
@@ -1175,7 +1226,7 @@ def main():
     # line, which stays one stream so that one step = one launch): the next
     # launch's workgroups start on the CUs the previous one has released.
     two_streams = None
-    if args.two_streams and rank == 0 and world == 1 and nbuf > 1:
+    if args.full and args.two_streams and rank == 0 and world == 1 and nbuf > 1:
         ss = [torch.cuda.Stream(device=dev) for _ in range(2)]
 
         def two(n):
@@ -1205,7 +1256,7 @@ def main():
     # link; the node-level rate is all ranks' bytes / the slowest rank's time.
     # Beside it, the link's ceiling: a plain pinned H2D copy of the same bytes.
     host = h2d = host_multi = host_latency = host_sweep = None
-    if not args.no_host:
+    if args.full and not args.no_host:
         pinned = torch.from_numpy(payload0).pin_memory()
         hp = pinned.numpy()
         hout = np.zeros(max(nout, 1), np.uint32)  # caller-owned output, as hadooprpc.c's packet buffer
@@ -1320,8 +1371,9 @@ def main():
                          "window_avg_us_all_steps": round(window_ms * 1e3, 2),
                          "algorithmic_bytes_per_launch": nbytes}, **roofline_node(nbytes, kernel_ms * 1e3, world)),
             "cpu_baseline": None,  # (filled in last: after every GPU timed region, below)
-            "bit_exact_vs_reference": bit_exact and timed_exact,
-            "bit_exact_checks": dict({"before_warmup_buf0": gate_exact}, **timed_checks),
+            "full": args.full,  # (False: the fields below that --full measures or checks are null)
+            "bit_exact_vs_reference": (bit_exact and timed_exact) if args.full else None,
+            "bit_exact_checks": dict({"before_warmup_buf0": gate_exact}, **timed_checks) if args.full else None,
             "host_resident_gib_s": host,
             "host_h2d_copy_gib_s": h2d,
             "host_resident_ranks": world if host is not None else None,
@@ -1345,7 +1397,7 @@ def main():
     # that raises is reported in its sub-object, and one that hangs (a
     # collective some rank never joins) or a teardown that does cannot cost
     # the main line.
-    sub = args.config == "c2" and args.scaling == "weak" and not (args.no_config4 and args.no_strong)
+    sub = args.full and args.config == "c2" and args.scaling == "weak" and not (args.no_config4 and args.no_strong)
     wd = SubRunWatchdog(args.sub_timeout_s, line) if sub else None
     if sub:
         wd.start()
@@ -1356,7 +1408,7 @@ def main():
     # The CPU baseline, last: rank 0's host cores once no rank has GPU work or
     # collectives left (at N > 1 the other ranks wait on the store), so it
     # neither competes with the timed regions nor holds peers in a collective.
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         line_set(line, "cpu_baseline", cpu_baseline_on_rank0(env, lambda: cpu_baseline(pk, payload0,
                                                                                       args.cpu_seconds)))
     if wd is not None:

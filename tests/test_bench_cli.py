@@ -41,6 +41,37 @@ def test_gpus_flag_must_be_positive():
     assert r.returncode != 0 and "--gpus" in r.stderr
 
 
+def test_extra_measurements_need_full():
+    """--two-streams / --host-sweep belong to --full: asked for without it
+    they are refused, not silently dropped."""
+    for flag in ("--two-streams", "--host-sweep"):
+        r = _run(["--gpus", "1", "--steps", "1", flag])
+        assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-2000:]
+        assert "{" not in r.stdout
+
+
+def test_dump_outputs_is_exact_and_samples_large_arrays_the_same_way(tmp_path):
+    """--dump-outputs: 32-bit checksums survive float64 exactly; an array past
+    the cap is cut to a fixed sample (the same indices in every run); rank
+    r > 0 writes a file of its own."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = np.array([0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF, 0xDEADBEEF], np.uint32)
+    bench.dump_outputs(str(tmp_path / "a"), 0, small.view(np.int32))  # (the device arrays are int32 views)
+    got = np.load(tmp_path / "a" / "checksums.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), small)
+    big = (np.arange(bench.DUMP_MAX_VALUES + 12345, dtype=np.uint64) * 2654435761 % (1 << 32)).astype(np.uint32)
+    bench.dump_outputs(str(tmp_path / "b"), 0, big)
+    bench.dump_outputs(str(tmp_path / "c"), 1, big)
+    b = np.load(tmp_path / "b" / "checksums.npy")
+    c = np.load(tmp_path / "c" / "checksums_rank1.npy")
+    assert b.shape == (bench.DUMP_MAX_VALUES,) and b.nbytes <= 64 << 20 and np.array_equal(b, c)
+    assert np.isin(b.astype(np.uint32), big).all() and len(np.unique(b)) > bench.DUMP_MAX_VALUES // 2
+
+
 def test_sub_run_error_is_reported_in_its_sub_object():
     """A sub-run that raises is recorded in its sub-object and the runs after
     it are skipped; the main line is still printed once (publish)."""

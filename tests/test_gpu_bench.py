@@ -37,7 +37,7 @@ def _line(out: str) -> dict:
 
 def test_bench_one_gpu_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "20",
-                        "--no-cpu", "--no-host"], cwd=ROOT, capture_output=True, text=True, timeout=300)
+                        "--full", "--no-cpu", "--no-host"], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = _line(r.stdout)
     sys.path.insert(0, ROOT)
@@ -65,13 +65,46 @@ def test_bench_one_gpu_contract():
     assert st["gib_s"] > 0 and 0 < st["frac_of_hbm_roofline_per_gpu"] < 1
 
 
+def test_bench_plain_run_times_the_steps_alone_and_dumps_the_last_output(tmp_path, hdfs):
+    """The plain command (no --full): the line holds the timed steps' figures
+    and none of the checks or extra runs, and --dump-outputs writes the
+    checksum array of the last timed step -- step 21 of 21 is on buffer 0
+    (PCG64 bytes of seed 2024), so the file is checked against the CPU path."""
+    out_dir = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "21", "--warmup", "5",
+                        "--dump-outputs", out_dir], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    assert len([ln for ln in r.stdout.splitlines() if ln.startswith("{")]) == 1
+    d = _line(r.stdout)
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+    from hdfs_crc32c_amd.workloads import config_packets, synthetic_bytes
+
+    assert bench.line_problems(d, want_cpu=False) == []
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 21 and d["warmup"] == 5
+    assert d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["dtype"] == "u32" and d["value"] > 0
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(0.25 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    assert 0 < d["roofline"]["frac"] < 1 and "hip graph" in d["launch"]
+    for key in ("cpu_baseline", "bit_exact_vs_reference", "bit_exact_checks", "verify", "box_read_probe", "config4",
+                "strong_scaling", "host_resident_gib_s", "host_resident_per_call", "eager_ms_per_step", "gather_ms"):
+        assert d[key] is None, key
+    assert os.listdir(out_dir) == ["checksums.npy"]
+    got = np.load(os.path.join(out_dir, "checksums.npy"))
+    pk, _ = config_packets("c2")
+    assert got.dtype == np.float64 and got.shape == (524288,)
+    want = bench.reference_checksums(synthetic_bytes(4096 * 65536, 2024), pk, 524288)
+    assert np.array_equal(got.astype(np.uint32), want) and np.array_equal(got, want.astype(np.float64))
+
+
 def test_bench_injected_capture_failure_falls_back_and_rebuilds():
     """BENCH_CAPTURE_FAIL_RANK=0 at N = 1, config 4 through RCCL (self-send):
     the step capture fails, the communicator is rebuilt, the steps are issued
     from the host and the gathered file is still bit-exact."""
     env = dict(os.environ, BENCH_CAPTURE_FAIL_RANK="0", BENCH_C4_SELF_SEND="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c4", "--steps", "20",
-                        "--warmup", "5", "--no-cpu", "--nbuf", "2", "--settle-ms", "20"], cwd=ROOT, env=env,
+                        "--warmup", "5", "--full", "--no-cpu", "--nbuf", "2", "--settle-ms", "20"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     c4 = _line(r.stdout)["config4"]
@@ -89,7 +122,7 @@ def test_bench_two_ranks_rehearsal(config):
     port = 29500 + random.randrange(2000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "20", "--warmup", "5", "--config", config, "--nbuf", "2"]
+           "--gpus", "2", "--steps", "20", "--warmup", "5", "--config", config, "--nbuf", "2", "--full"]
     cmd += ["--cpu-seconds", "0.3"] if config == "c2" else ["--no-cpu"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -125,7 +158,8 @@ def test_bench_config4_line_two_ranks_complete():
     port = 29500 + random.randrange(2000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "10", "--warmup", "2", "--config", "c4", "--nbuf", "2", "--cpu-seconds", "0.3"]
+           "--gpus", "2", "--steps", "10", "--warmup", "2", "--config", "c4", "--nbuf", "2", "--cpu-seconds", "0.3",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = _line(r.stdout)
@@ -144,7 +178,8 @@ def test_bench_two_ranks_capture_failure_on_one_rank():
     port = 29500 + random.randrange(2000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-host", "--nbuf", "2", "--no-config4"]
+           "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu", "--no-host", "--nbuf", "2",
+           "--no-config4"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = _line(r.stdout)
@@ -160,7 +195,7 @@ def test_bench_gpus_flag_spawns_ranks():
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c2", "--steps", "20",
-                        "--warmup", "5", "--no-cpu", "--nbuf", "2"], cwd=ROOT, env=env, capture_output=True,
+                        "--warmup", "5", "--full", "--no-cpu", "--nbuf", "2"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = _line(r.stdout)

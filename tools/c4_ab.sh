@@ -12,7 +12,7 @@ for rep in ${REPS:-1 2}; do
       w=$([ "$steps" -gt 100 ] && echo 500 || echo 5)
       f=$OUT/c4_p${pipe}_s${steps}_r${rep}.json
       BENCH_C4_PIPELINE=$pipe timeout -k 10 300 python bench.py --config c4 --steps "$steps" --warmup "$w" \
-        --no-cpu --no-host > "$f" 2> "$f.err"
+        --full --no-cpu --no-host > "$f" 2> "$f.err"
       rc=$?
       echo "pipe=$pipe steps=$steps rep=$rep rc=$rc"
       [ $rc -ne 0 ] && { tail -5 "$f.err"; exit $rc; }

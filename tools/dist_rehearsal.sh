@@ -10,7 +10,7 @@ mkdir -p gpurun_out
 export MASTER_ADDR=127.0.0.1 BENCH_DIST_BACKEND=gloo
 for cfg in c2 c5; do
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-      --master-port $((29500 + RANDOM % 1000)) bench.py --gpus 2 --steps 10 --warmup 3 --config $cfg --no-cpu --no-host \
+      --master-port $((29500 + RANDOM % 1000)) bench.py --gpus 2 --steps 10 --warmup 3 --config $cfg --full --no-cpu --no-host \
       > gpurun_out/dist_$cfg.log 2>&1 || { echo "dist $cfg failed rc=$?"; tail -20 gpurun_out/dist_$cfg.log; exit 1; }
   grep '^{' gpurun_out/dist_$cfg.log | tail -1
 done

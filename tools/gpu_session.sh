@@ -23,19 +23,19 @@ for s in $STEPS; do
   case $s in
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) run tests ${T_TIMEOUT:-900} python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ${T_ARGS:-} ;;
-    bench) run bench 600 python bench.py ${BENCH_ARGS:-} ;;
-    bench5) run bench5 600 python bench.py --config c5 --no-cpu ;;
-    bench3) run bench3 600 python bench.py --config c3 --no-cpu --no-host ;;
-    bench4) run bench4 600 python bench.py --config c4 --no-cpu --no-host ;;
-    cfgs) for c in ${CFGS:-c3 c2b1536 c4 c5}; do run bench_$c 600 python bench.py --config $c --no-cpu --no-host ${CFG_ARGS:-}; done ;;
+    bench) run bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
+    bench5) run bench5 600 python bench.py --full --config c5 --no-cpu ;;
+    bench3) run bench3 600 python bench.py --full --config c3 --no-cpu --no-host ;;
+    bench4) run bench4 600 python bench.py --full --config c4 --no-cpu --no-host ;;
+    cfgs) for c in ${CFGS:-c3 c2b1536 c4 c5}; do run bench_$c 600 python bench.py --full --config $c --no-cpu --no-host ${CFG_ARGS:-}; done ;;
     pmc) run pmc 1100 bash tools/pmc_session.sh ;;
     stamps) for v in ${SV:-5 6}; do run stamps_${SCFG:-c2}_v$v 300 python tools/stamps.py ${SCFG:-c2} $v ${SW:-12}; done ;;
     tprobe) run tprobe 300 python tools/timing_probe.py ;;
     sweep) run sweep 300 python tools/probe_sweep.py ;;
     kbench) run kbench_${KCFG:-c2} ${KB_TIMEOUT:-600} python tools/kbench.py --config ${KCFG:-c2} --variants ${KV:-0,1,2,3,4,5} ${KB_ARGS:-} ;;
     kbench5) run kbench5 600 python tools/kbench.py --config c5 --variants ${KV:-0,1} ;;
-    bench3h) run bench3h 600 python bench.py --config c3 --host-sweep --cpu-seconds 2 ;;
-    sweepab) run sweep_zc0 600 env HDFS_CRC32C_ZERO_COPY_KB=0 python bench.py --config c3 --host-sweep --no-cpu --steps 200 --warmup 50 && run sweep_zc 600 python bench.py --config c3 --host-sweep --no-cpu --steps 200 --warmup 50 ;;
+    bench3h) run bench3h 600 python bench.py --full --config c3 --host-sweep --cpu-seconds 2 ;;
+    sweepab) run sweep_zc0 600 env HDFS_CRC32C_ZERO_COPY_KB=0 python bench.py --full --config c3 --host-sweep --no-cpu --steps 200 --warmup 50 && run sweep_zc 600 python bench.py --full --config c3 --host-sweep --no-cpu --steps 200 --warmup 50 ;;
     brate) run brate 300 tools/block_rate ${BR_ARGS:-16 400 16 30} ;;
     brateab) run brate_rec 300 env HDFS_CRC32C_QUEUE_RECORD=1 tools/block_rate ${BR_ARGS:-16 400 16 30} && run brate 300 tools/block_rate ${BR_ARGS:-16 400 16 30} ;;
     ab02) for c in ${ABCFGS:-c5 c2b1536}; do
