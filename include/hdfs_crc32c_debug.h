@@ -32,6 +32,10 @@ extern "C" {
  * *ngen. */
 int crc32c_debug_plan(const crc32c_packet *pkts, size_t npkts, void *tiles, size_t tiles_cap, void *gen,
                       size_t gen_cap, uint64_t *ntiles, uint64_t *ngen);
+/* The same with absolute != 0: the items of a plan whose payload offsets are
+ * device addresses (CRC32C_DEVICE_ADDRESSES), before it is rebased. */
+int crc32c_debug_plan_abs(const crc32c_packet *pkts, size_t npkts, int absolute, void *tiles, size_t tiles_cap,
+                          void *gen, size_t gen_cap, uint64_t *ntiles, uint64_t *ngen);
 
 /* Item counts of a crc32c_plan_create_buffers plan (CRC32C): counts[0..5] =
  * tiles, gen items, seg items, pieces, constant runs, checksums. */
@@ -70,6 +74,41 @@ int crc32c_debug_blocks_worker_cpu_ns(crc32c_blocks *q, uint64_t *ns);
 /* The device address of the pooled block holding a plan's descriptors (0:
  * none): tests see a destroyed plan's block come back from the pool. */
 uint64_t crc32c_debug_plan_block(const crc32c_plan *plan);
+
+/* The production kernel build a launch runs: the instantiation
+ * hdfs_crc32c_plan_kernel<threads, waves_per_simd, mode> (mode: the kernel's
+ * template bits, csrc/plan_select.h), the units each tile is split into (4
+ * quarter, 2 half, 1 whole) and the workgroups launched. */
+typedef struct crc32c_debug_build {
+    uint32_t threads, waves_per_simd, mode, units_per_tile, grid;
+} crc32c_debug_build;
+
+/* The build the library's launch path chooses for these item counts and
+ * `general` bits (1 general tiles, 2 shifted loads, 4 half tiles, 8 padded
+ * power-of-two tiles) on num_cu CUs; verify != 0: the comparing twin.  Pure
+ * host arithmetic, no GPU.  -EINVAL for num_cu == 0 or out == NULL. */
+int crc32c_debug_select_build(uint32_t ntiles, uint32_t ngen, uint32_t nseg, uint32_t nconst, uint32_t general,
+                              int verify, uint32_t num_cu, crc32c_debug_build *out);
+
+/* What crc32c_plan_exec (verify != 0: crc32c_plan_verify) of this plan on
+ * dev_payload would hand the kernel -- item counts, the `general` bits (the
+ * payload pointer's own misalignment included), skip_z (1: the launch stages
+ * the table image without its Z^(512 s) section) -- the CU count the launch
+ * is sized for, and the build chosen from them by the same selector.
+ * Launches nothing.  A device-address plan takes dev_payload = NULL. */
+typedef struct crc32c_debug_launch_info {
+    uint32_t ntiles, ngen, nseg, nconst, general, skip_z, num_cu, reserved;
+    crc32c_debug_build build;
+} crc32c_debug_launch_info;
+int crc32c_debug_plan_launch_info(const crc32c_plan *plan, const void *dev_payload, int verify,
+                                  crc32c_debug_launch_info *out);
+
+/* The launch-path predicates over the work items of a packet batch
+ * (absolute != 0: payload offsets are device addresses): *general_bits as a
+ * plan of these packets on a 16-byte aligned payload would set them, and
+ * *needs_z = 1 when some item shifts by Z^(512 s).  No GPU. */
+int crc32c_debug_packets_flags(const crc32c_packet *pkts, size_t npkts, int absolute, uint32_t *general_bits,
+                               int *needs_z);
 
 /* ---- 2. libhdfs_crc32c_debug.so only ---- */
 
@@ -115,6 +154,18 @@ int crc32c_debug_resident_stats(const crc32c_resident *r, uint64_t *launches);
  * trips (ticks). -EINVAL without the trace. */
 int crc32c_debug_resident_trace(crc32c_resident *r, uint64_t *stamps, uint64_t *rtt_ticks, uint64_t *rtt_polls);
 int crc32c_debug_resident_destroy(crc32c_resident *r);
+
+/* Cold-LDS tests (debug/lds_poison.hip).  Poison: 4 x CUs workgroups of 256
+ * threads, each holding a CU's whole LDS (163 840 bytes: one fits per CU),
+ * write word i of it with (seed ^ i * 0x9E3779B9) | 1 -- a kernel launched
+ * next on the stream that stages too little of its table image reads this
+ * instead of the image an earlier launch left.  Peek: the same grid counts,
+ * per workgroup, the words still holding that pattern into dev_counts (one
+ * u32 per workgroup, zeroed by the call on the stream).  Both return the
+ * number of workgroups (peek with dev_counts == NULL: that only, no launch)
+ * or -errno; they run on the current device. */
+int crc32c_debug_lds_poison(uint32_t seed, void *stream);
+int crc32c_debug_lds_peek(uint32_t seed, uint32_t *dev_counts, void *stream);
 
 #ifdef __cplusplus
 }

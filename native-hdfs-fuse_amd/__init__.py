@@ -56,6 +56,23 @@ class FramesResult(ctypes.Structure):
                 ("last_packet", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class DebugBuild(ctypes.Structure):
+    """crc32c_debug_build: hdfs_crc32c_plan_kernel<threads, waves_per_simd, mode> and its grid."""
+    _fields_ = [("threads", ctypes.c_uint32), ("waves_per_simd", ctypes.c_uint32), ("mode", ctypes.c_uint32),
+                ("units_per_tile", ctypes.c_uint32), ("grid", ctypes.c_uint32)]
+
+    @property
+    def kernel(self):
+        return int(self.threads), int(self.waves_per_simd), int(self.mode)
+
+
+class DebugLaunchInfo(ctypes.Structure):
+    """crc32c_debug_launch_info: the KParams facts of a plan launch and the build chosen from them."""
+    _fields_ = [("ntiles", ctypes.c_uint32), ("ngen", ctypes.c_uint32), ("nseg", ctypes.c_uint32),
+                ("nconst", ctypes.c_uint32), ("general", ctypes.c_uint32), ("skip_z", ctypes.c_uint32),
+                ("num_cu", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("build", DebugBuild)]
+
+
 class Crc32cError(RuntimeError):
     def __init__(self, rc: int, msg: str):
         super().__init__("%s (rc=%d %s)" % (msg, rc, errno.errorcode.get(-rc, "?")))
@@ -111,6 +128,10 @@ def debug_lib():
         L.crc32c_debug_stream_probe.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint32, i32, vp]
         L.crc32c_debug_variant_name.restype = ctypes.c_char_p
         L.crc32c_debug_variant_name.argtypes = [i32, ctypes.POINTER(i32)]
+        L.crc32c_debug_lds_poison.restype = i32
+        L.crc32c_debug_lds_poison.argtypes = [ctypes.c_uint32, vp]
+        L.crc32c_debug_lds_peek.restype = i32
+        L.crc32c_debug_lds_peek.argtypes = [ctypes.c_uint32, vp, vp]
         u64p = ctypes.POINTER(ctypes.c_uint64)
         for name, args in (("crc32c_debug_resident_create", [vp, ctypes.c_uint32, ctypes.POINTER(vp)]),
                            ("crc32c_debug_resident_submit", [vp, vp, vp, u64p]),
@@ -162,6 +183,25 @@ class Resident:
             pass
 
 
+def debug_lds_poison(seed: int, stream=0) -> int:
+    """crc32c_debug_lds_poison (debug library): every CU's LDS filled with the seed's
+    pattern by a launch on ``stream``; returns the workgroups launched."""
+    n = int(debug_lib().crc32c_debug_lds_poison(seed & 0xFFFFFFFF, ctypes.c_void_p(_stream_handle(stream, {}))))
+    if n < 0:
+        _check(n, "crc32c_debug_lds_poison")
+    return n
+
+
+def debug_lds_peek(seed: int, dev_counts: int = 0, stream=0) -> int:
+    """crc32c_debug_lds_peek (debug library): per workgroup, the LDS words still holding the
+    seed's pattern, into dev_counts (u32 each); returns the workgroups (dev_counts 0: only that)."""
+    n = int(debug_lib().crc32c_debug_lds_peek(seed & 0xFFFFFFFF, ctypes.c_void_p(dev_counts),
+                                              ctypes.c_void_p(_stream_handle(stream, {}))))
+    if n < 0:
+        _check(n, "crc32c_debug_lds_peek")
+    return n
+
+
 def variant_info(v: int):
     """(name, exact) of a kernel variant built into the debug library, or None."""
     ex = ctypes.c_int(0)
@@ -194,6 +234,7 @@ def _bind(L):
         "crc32c_multi_batch_host": (i32, [vp, vp, vp, sz, u32, vp, u32]),
         "crc32c_last_error": (ctypes.c_char_p, []),
         "crc32c_debug_plan": (i32, [vp, sz, vp, sz, vp, sz, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "crc32c_debug_plan_abs": (i32, [vp, sz, i32, vp, sz, vp, sz, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "crc32c_debug_lds_image": (sz, [vp, sz, vp, vp]),
         "crc32c_debug_lds_image_s4": (sz, [vp, sz, u32]),
         "crc32c_plan_verify": (i32, [vp, vp, vp, vp, vp]),
@@ -236,6 +277,9 @@ def _bind(L):
         "crc32c_debug_blocks_fail_flushes": (i32, [vp, u32]),
         "crc32c_debug_blocks_resident_inject": (i32, [vp, i32, u32]),
         "crc32c_verify_frames_host": (i32, [vp, vp, sz, u32, u64, u32, ctypes.POINTER(FramesResult)]),
+        "crc32c_debug_select_build": (i32, [u32, u32, u32, u32, u32, i32, u32, ctypes.POINTER(DebugBuild)]),
+        "crc32c_debug_plan_launch_info": (i32, [vp, vp, i32, ctypes.POINTER(DebugLaunchInfo)]),
+        "crc32c_debug_packets_flags": (i32, [vp, sz, i32, ctypes.POINTER(u32), ctypes.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -463,6 +507,13 @@ class Plan:
                                                           ctypes.c_void_p(dev_out), ctypes.c_void_p(dev_stamps),
                                                           variant, ctypes.c_void_p(stream)),
                "crc32c_debug_plan_exec_variant")
+
+    def launch_info(self, dev_payload: int = 0, verify: bool = False) -> DebugLaunchInfo:
+        """crc32c_debug_plan_launch_info: what exec (or verify) on dev_payload would launch; launches nothing."""
+        info = DebugLaunchInfo()
+        _check(lib().crc32c_debug_plan_launch_info(self.handle, ctypes.c_void_p(dev_payload), int(verify),
+                                                   ctypes.byref(info)), "crc32c_debug_plan_launch_info")
+        return info
 
     def close(self) -> None:
         if self.handle:
@@ -785,17 +836,37 @@ def total_checksums(pkts) -> int:
     return int(lib().crc32c_batch_nchecksums(_np_ptr(pkts), pkts.size))
 
 
-def debug_plan(pkts):
-    """Work items a plan would upload (FastTile / GenItem arrays)."""
+def debug_plan(pkts, absolute: bool = False):
+    """Work items a plan would upload (FastTile / GenItem arrays); absolute:
+    of a CRC32C_DEVICE_ADDRESSES plan, before it is rebased."""
     pkts = as_packets(pkts)
     nt, ng = ctypes.c_uint64(), ctypes.c_uint64()
-    _check(lib().crc32c_debug_plan(_np_ptr(pkts), pkts.size, None, 0, None, 0, ctypes.byref(nt), ctypes.byref(ng)),
-           "crc32c_debug_plan")
+    _check(lib().crc32c_debug_plan_abs(_np_ptr(pkts), pkts.size, int(absolute), None, 0, None, 0, ctypes.byref(nt),
+                                       ctypes.byref(ng)), "crc32c_debug_plan")
     tiles = np.zeros(max(nt.value, 1), TILE_DTYPE)
     gen = np.zeros(max(ng.value, 1), GEN_DTYPE)
-    _check(lib().crc32c_debug_plan(_np_ptr(pkts), pkts.size, _np_ptr(tiles), nt.value, _np_ptr(gen), ng.value,
-                                   ctypes.byref(nt), ctypes.byref(ng)), "crc32c_debug_plan")
+    _check(lib().crc32c_debug_plan_abs(_np_ptr(pkts), pkts.size, int(absolute), _np_ptr(tiles), nt.value,
+                                       _np_ptr(gen), ng.value, ctypes.byref(nt), ctypes.byref(ng)),
+           "crc32c_debug_plan")
     return tiles[: nt.value], gen[: ng.value]
+
+
+def debug_select_build(ntiles: int, ngen: int, nseg: int, nconst: int, general: int, verify: bool,
+                       num_cu: int) -> DebugBuild:
+    """crc32c_debug_select_build: the production build the launch path chooses (no GPU)."""
+    b = DebugBuild()
+    _check(lib().crc32c_debug_select_build(ntiles, ngen, nseg, nconst, general, int(verify), num_cu, ctypes.byref(b)),
+           "crc32c_debug_select_build")
+    return b
+
+
+def debug_packets_flags(pkts, absolute: bool = False):
+    """crc32c_debug_packets_flags: (KParams general bits, needs_z) of a packet batch's plan (no GPU)."""
+    pkts = as_packets(pkts)
+    g, z = ctypes.c_uint32(0), ctypes.c_int(0)
+    _check(lib().crc32c_debug_packets_flags(_np_ptr(pkts), pkts.size, int(absolute), ctypes.byref(g), ctypes.byref(z)),
+           "crc32c_debug_packets_flags")
+    return int(g.value), bool(z.value)
 
 
 def debug_lds_image():

@@ -82,39 +82,8 @@ constexpr uint32_t kS4ShiftOff = uint32_t(hdfs_crc::kS4ShiftOff);
 constexpr uint32_t kS4StageBytes = (kS4Bytes + 1023u) / 1024u * 1024u;
 static_assert(kS4StageBytes <= hdfs_crc::kTableAllocS4, "staging reads past the device table");
 
-// Kernel modes (template bits).  Production = kModeS4 | kModeNt (+ kModeVerify).
-constexpr int kModeNt = 1;          // payload loads non-temporal (streamed once)
-constexpr int kModeS4 = 2;          // slicing-by-4 chains + per-column finishing operator (S4 image)
-constexpr int kModeStamps = 4;      // DIAGNOSTIC: per-wave timestamps
-constexpr int kModeMemDiag = 8;     // DIAGNOSTIC, wrong results: no lookups (memory ceiling)
-constexpr int kModeCompDiag = 16;   // DIAGNOSTIC, wrong results: no payload loads (compute ceiling)
-constexpr int kModeNoStage = 32;    // DIAGNOSTIC (memory-only): no table staging
-constexpr int kModeVerify = 64;     // read side: compare with p.expect[] instead of storing (crc32c_plan_verify)
-constexpr int kModeS4C = 512;      // small batches: compact S4 image (T0..T3 once, 28 KiB staged)
-constexpr int kModeEarly = 1024;    // the first tile's loads are issued before the table staging
-constexpr int kModeHalves = 16384;  // with kModeQuarter, 2 units of 8 blocks per tile instead of 4 (3-6 tiles per CU)
-constexpr int kModeQuarter = 4096;  // small batches: power-of-two tiles of chunks <= 2 KiB run as 4 work
-                                    // units of 4 blocks each (4x the waves, 1/4 of each wave's latency chain)
-constexpr int kModeXcdMap = 2048;   // A/B: workgroup ranges remapped so that each XCD's workgroups hold one
-                                    // contiguous 1/8 of the batch (instead of every eighth range)
-constexpr int kModeGDiagNoGather = 128;  // DIAGNOSTIC, wrong results: general items skip the per-subtile gather
-constexpr int kModeGDiagNoMask = 8192;   // DIAGNOSTIC, wrong results: general items skip the chunk-start masks
-constexpr int kModeGeneral = 256;   // the batch has general tiles (a plan without them runs the kernel without
-                                    // their code: the power-of-two tile loop stays as compact as round 1's)
-// (with kModeGeneral) the batch has no shifted tiles / no general tiles: the
-// build leaves that code out, so the other path gets the registers and the
-// schedule to itself
-constexpr int kModeNoShift = 32768;
-constexpr int kModeNoGItems = 65536;
-constexpr int kModeGHoist = 131072;  // a general item's next subtile facts computed before this subtile's lookups
-                                     // (the both-paths general build: padded chunks 0.5-2 % faster, round 5)
-constexpr int kModeGGroup2 = 262144;  // A/B: (with kModeNoShift) general items gathered 2 subtiles at a time, not 4
-constexpr int kModeHalfT = 1048576;   // (with kModeGeneral) the build also runs half tiles (their own builds: the
-                                      // code costs the other general builds 3-8 %, round 5)
-constexpr int kModeNoPadT = 2097152;  // (general builds) no padded power-of-two tiles: the production small-batch
-                                      // builds (their code there cost config 3 ~4 %, round 5)
-constexpr int kModeOvl = 524288;      // A/B: the first tile's loads issued right after the table staging's, before
-                                      // the barrier that waits for the staging (their latencies overlap)
+// (The kernel modes -- template bits kMode* -- are in plan_select.h, with the
+// choice of production build.)
 // GEN bits of the tile helpers below: general tiles, shifted (unaligned)
 // tiles, general items gathered 4 subtiles at a time (finish_gtile GROUP)
 constexpr int kGenItems = 1, kGenShift = 2, kGenGroup4 = 4, kGenGroup2 = 8, kGenHoist = 16, kGenHalf = 32,
@@ -1235,12 +1204,8 @@ __global__ __launch_bounds__(THREADS, WPS) void hdfs_crc32c_plan_kernel(hdfs_crc
 }
 
 namespace hdfs_crc {
-// Grid of a launch: one workgroup per CU, or one per work item when there
-// are fewer items than CUs (a small batch leaves most waves without a tile;
-// they still share the table staging, which is what bounds a small launch).
+// Grid of a launch of p (plan_select.h production_grid over its items).
 inline uint32_t production_grid(const KParams &p, uint32_t num_cu, uint32_t units_per_tile = 1) {
-    const uint64_t items = uint64_t(p.ntiles) * units_per_tile + (uint64_t(p.ngen) + 1) / 2 +
-                           (uint64_t(p.nseg) + 1) / 2 + p.nconst;
-    return uint32_t(items < num_cu ? (items ? items : 1) : num_cu);
+    return production_grid(launch_items(p.ntiles, p.ngen, p.nseg, p.nconst, units_per_tile), num_cu);
 }
 }  // namespace hdfs_crc

@@ -43,31 +43,8 @@
 
 namespace hdfs_crc {
 
-namespace {
-// Work items per CU up to which the compact image wins: its T lookups are
-// not conflict-free (one copy of each table instead of 32 lane columns), so
-// once every CU has many tiles the full image's faster lookups pay back its
-// staging (small batches; graph-replayed, 3072 tiles:
-// 7.89 vs 8.24 us, 4096: 9.05 vs 9.39, 8192: full image ahead,
-// profiles/r02/launch_probe_units_crossover.json).
-constexpr uint64_t kSmallBatchItemsPerCu = 16;
-// Tiles per CU up to which quarter units win (tools/launch_probe.py,
-// profiles/r02/launch_probe_crossover.json: 512 tiles 3.71 vs 4.36 us, 768
-// tiles 4.24 vs 4.72, 1024 tiles 5.56 vs 4.95).
-constexpr uint64_t kQuarterTilesPerCu = 3;
-// Tiles per CU up to which the quarter-unit build issues the first unit's
-// loads before the table staging (tools/launch_probe.py, debug variants 82 /
-// 83, profiles/r06/early/: 512 tiles 3.57 vs 3.71-3.74 us, 768 tiles
-// 4.41-4.46 vs 4.16-4.22).
-constexpr uint64_t kEarlyTilesPerCu = 2;
-// Tiles per CU up to which half units win over whole tiles (debug variant
-// 86 against production, tools/launch_probe.py, profiles/r06/halves/: 1280
-// tiles 5.50-5.55 vs 5.95-5.98 us, 1536 5.73-5.79 vs 6.09-6.16, 1792
-// 6.80-6.84 vs 6.56-6.58, 2048 7.02-7.13 vs 6.79-6.94).  (Round 2 measured
-// halves only with the padded-tile code in the build: 2-5 %.)
-constexpr uint64_t kHalvesTilesPerCu = 6;
-}  // namespace
-
+// Launches the instantiation select_plan_build (plan_select.h, with the
+// thresholds and their measurements) names for p, on the grid it gives.
 hipError_t launch_plan_kernel(const KParams &p, uint32_t num_cu, hipStream_t stream, hipEvent_t stop,
                               uint32_t *grid) {
     using namespace hdfs_crc_dev;
@@ -75,79 +52,36 @@ hipError_t launch_plan_kernel(const KParams &p, uint32_t num_cu, hipStream_t str
     constexpr int kGen = kModeGeneral;
     constexpr int kSmall = kModeS4C | kModeGeneral | kModeNoPadT;
     constexpr int kQuarter = kSmall | kModeQuarter;
-    const uint64_t items = uint64_t(p.ntiles) + (uint64_t(p.ngen) + 1) / 2 + (uint64_t(p.nseg) + 1) / 2 + p.nconst;
-    const bool half = (p.general & kGeneralHalf) != 0;  // (half tiles: builds of their own, full image)
-    // (padded power-of-two tiles and half tiles only run in full-image
-    // builds: their code in the small-batch builds cost config 3 ~4 %)
-    const bool small = !half && !(p.general & kGeneralPadded) && items <= kSmallBatchItemsPerCu * num_cu;
-    const bool quarter = small && p.ntiles <= kQuarterTilesPerCu * num_cu;
-    const bool early = quarter && p.ntiles <= kEarlyTilesPerCu * num_cu;
-    const bool halves = small && !quarter && p.ntiles <= kHalvesTilesPerCu * num_cu;
-    const dim3 g{production_grid(p, num_cu, quarter ? 4u : halves ? 2u : 1u), 1, 1}, b{768, 1, 1};
+    const PlanBuild sel = select_plan_build(p.ntiles, p.ngen, p.nseg, p.nconst, p.general, p.expect != nullptr, num_cu);
+    const dim3 g{sel.grid, 1, 1}, b{sel.threads, 1, 1};
     if (grid) *grid = g.x;
-#define LAUNCH_B(K, B)                                                             \
-    do {                                                                           \
-        if (stop)                                                                  \
-            hipExtLaunchKernelGGL(K, g, B, 0, stream, nullptr, stop, 0u, p);       \
-        else                                                                       \
-            hipLaunchKernelGGL(K, g, B, 0, stream, p);                             \
-    } while (0)
-#define LAUNCH(K) LAUNCH_B(K, b)
-    const dim3 b8{512, 1, 1};  // (the aligned one-block form: 8 waves)
-    // Half tiles run in builds of their own, any batch size (the full image):
-    // with the shifted loads only where some tile is off 16-byte alignment
-    // (padded general items -- a packet's tail -- do not need them there).
-    const bool half_shift = half && (p.general & kGeneralShift) != 0;
-    if (p.expect) {
-        if (!p.result || !p.sched) return hipErrorInvalidValue;
-        if (half_shift)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeGHoist | kModeHalfT | kModeVerify>));
-        else if (half)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeNoShift | kModeHalfT | kModeVerify>));
-        else if (early && !p.general)
-            LAUNCH_B((hdfs_crc32c_plan_kernel<512, 2, kProd | kModeS4C | kModeQuarter | kModeEarly | kModeVerify>), b8);
-        else if (early)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kQuarter | kModeEarly | kModeVerify>));
-        else if (quarter)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kQuarter | kModeVerify>));
-        else if (halves)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kQuarter | kModeHalves | kModeVerify>));
-        else if (small)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kSmall | kModeVerify>));
-        else if (p.general == kGeneralItems)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeNoShift | kModeVerify>));
-        else if (p.general == kGeneralShift)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeNoGItems | kModeVerify>));
-        else if (p.general)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeGHoist | kModeVerify>));
-        else
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kModeVerify>));
-    } else {
-        if (half_shift)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeGHoist | kModeHalfT>));
-        else if (half)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeNoShift | kModeHalfT>));
-        else if (early && !p.general)
-            LAUNCH_B((hdfs_crc32c_plan_kernel<512, 2, kProd | kModeS4C | kModeQuarter | kModeEarly>), b8);
-        else if (early)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kQuarter | kModeEarly>));
-        else if (quarter)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kQuarter>));
-        else if (halves)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kQuarter | kModeHalves>));
-        else if (small)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kSmall>));
-        else if (p.general == kGeneralItems)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeNoShift>));
-        else if (p.general == kGeneralShift)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeNoGItems>));
-        else if (p.general)
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd | kGen | kModeGHoist>));
-        else
-            LAUNCH((hdfs_crc32c_plan_kernel<768, 3, kProd>));
+    if (p.expect && (!p.result || !p.sched)) return hipErrorInvalidValue;
+    // Every production build, exec and verify twin: the kernels of the product library.
+#define BUILD(T, W, M)                                                                                          \
+    case (M):                                                                                                   \
+        if (sel.threads != T || sel.waves_per_simd != W) return hipErrorInvalidValue;                           \
+        if (stop)                                                                                               \
+            hipExtLaunchKernelGGL((hdfs_crc32c_plan_kernel<T, W, (M)>), g, b, 0, stream, nullptr, stop, 0u, p); \
+        else                                                                                                    \
+            hipLaunchKernelGGL((hdfs_crc32c_plan_kernel<T, W, (M)>), g, b, 0, stream, p);                       \
+        break;
+#define BUILD2(T, W, M) BUILD(T, W, M) BUILD(T, W, (M) | kModeVerify)
+    switch (sel.mode) {
+        BUILD2(768, 3, kProd | kGen | kModeGHoist | kModeHalfT)
+        BUILD2(768, 3, kProd | kGen | kModeNoShift | kModeHalfT)
+        BUILD2(512, 2, kProd | kModeS4C | kModeQuarter | kModeEarly)
+        BUILD2(768, 3, kProd | kQuarter | kModeEarly)
+        BUILD2(768, 3, kProd | kQuarter)
+        BUILD2(768, 3, kProd | kQuarter | kModeHalves)
+        BUILD2(768, 3, kProd | kSmall)
+        BUILD2(768, 3, kProd | kGen | kModeNoShift)
+        BUILD2(768, 3, kProd | kGen | kModeNoGItems)
+        BUILD2(768, 3, kProd | kGen | kModeGHoist)
+        BUILD2(768, 3, kProd)
+    default: return hipErrorInvalidValue;  // (a build the selector names and this library does not hold)
     }
-#undef LAUNCH
-#undef LAUNCH_B
+#undef BUILD2
+#undef BUILD
     return hipGetLastError();
 }
 

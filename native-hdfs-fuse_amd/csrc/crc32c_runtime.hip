@@ -146,6 +146,13 @@ static bool has_misaligned(const HostPlan &hp) {
     return false;
 }
 
+// KParams::general of a launch over hp's items on a 16-byte aligned payload.
+static uint32_t general_bits(const HostPlan &hp) {
+    return (has_general(hp) ? kGeneralItems : 0u) |
+           ((has_misaligned(hp) || (has_padded_general(hp) && !has_half(hp))) ? kGeneralShift : 0u) |
+           (has_half(hp) ? kGeneralHalf : 0u) | (has_padded_tiles(hp) ? kGeneralPadded : 0u);
+}
+
 KParams plan_params(const crc32c_plan *plan, const void *payload, uint32_t *out) {
     KParams p = base_params(plan->ctx, payload, out, plan->flags);
     const DevicePlan &dp = plan->dp;
@@ -511,6 +518,18 @@ int alloc_slots(SchedSlots &s) {
     return 0;
 }
 
+// The CUs a launch is sized for.
+// (A/B knob HDFS_CRC32C_CU_CAP=n: launches size their grid for at most n
+// CUs, leaving the rest to kernels beside them -- an RCCL group
+// overlapping a pipelined multi-plan step; measured no gain)
+uint32_t launch_cus(const crc32c_ctx *ctx) {
+    static const int cap = [] {
+        const char *e = std::getenv("HDFS_CRC32C_CU_CAP");
+        return e ? std::atoi(e) : 0;
+    }();
+    return uint32_t(cap > 0 && cap < ctx->num_cu ? cap : ctx->num_cu);
+}
+
 // Launches p on `stream`.  Verification launches use the sequence's slot
 // (left reset by the previous one); the caller keeps launches on `slots`
 // in GPU order.  *grid: the workgroups launched (0: none).
@@ -528,15 +547,7 @@ int launch(const crc32c_ctx *ctx, KParams p, SchedSlots &slots, hipStream_t stre
         if (rc) return rc;
         p.sched = slots.d;
     }
-    // (A/B knob HDFS_CRC32C_CU_CAP=n: launches size their grid for at most n
-    // CUs, leaving the rest to kernels beside them -- an RCCL group
-    // overlapping a pipelined multi-plan step; measured no gain)
-    static const int cap = [] {
-        const char *e = std::getenv("HDFS_CRC32C_CU_CAP");
-        return e ? std::atoi(e) : 0;
-    }();
-    const uint32_t ncu = uint32_t(cap > 0 && cap < ctx->num_cu ? cap : ctx->num_cu);
-    HIP_TRY(launch_plan_kernel(p, ncu, stream, stop, grid));
+    HIP_TRY(launch_plan_kernel(p, launch_cus(ctx), stream, stop, grid));
     return 0;
 }
 
@@ -840,9 +851,7 @@ int batch_host_locked(crc32c_ctx *ctx, const uint8_t *payload, const crc32c_pack
         p.ngen = uint32_t(plan.gen.size());
         // (the staged slices keep every packet's 16-byte phase: tiles off
         // alignment take the general build's shifted loads, as in plans)
-        p.general = (has_general(plan) ? kGeneralItems : 0u) |
-                    ((has_misaligned(plan) || (has_padded_general(plan) && !has_half(plan))) ? kGeneralShift : 0u) |
-                    (has_half(plan) ? kGeneralHalf : 0u) | (has_padded_tiles(plan) ? kGeneralPadded : 0u);
+        p.general = general_bits(plan);
         p.skip_z = needs_z(plan) ? 0u : 1u;
         rc = launch(ctx, p, s.sched, s.stream);
         if (rc) return rc;
@@ -1253,6 +1262,48 @@ uint64_t crc32c_debug_plan_block(const crc32c_plan *plan) {
     return plan ? uint64_t(reinterpret_cast<uintptr_t>(plan->dp.d)) : 0;
 }
 uint64_t crc32c_plan_payload_bytes(const crc32c_plan *plan) { return plan ? plan->payload_bytes : 0; }
+
+static void put_build(const PlanBuild &b, crc32c_debug_build *out) {
+    out->threads = b.threads;
+    out->waves_per_simd = b.waves_per_simd;
+    out->mode = uint32_t(b.mode);
+    out->units_per_tile = b.units_per_tile;
+    out->grid = b.grid;
+}
+
+int crc32c_debug_select_build(uint32_t ntiles, uint32_t ngen, uint32_t nseg, uint32_t nconst, uint32_t general,
+                              int verify, uint32_t num_cu, crc32c_debug_build *out) {
+    if (!out || !num_cu) return fail(-EINVAL, "out == NULL or num_cu == 0");
+    put_build(select_plan_build(ntiles, ngen, nseg, nconst, general, verify != 0, num_cu), out);
+    return 0;
+}
+
+int crc32c_debug_plan_launch_info(const crc32c_plan *plan, const void *dev_payload, int verify,
+                                  crc32c_debug_launch_info *out) {
+    if (!plan || !out) return fail(-EINVAL, "plan/out == NULL");
+    if (int rc = plan_payload(plan, &dev_payload)) return rc;
+    const KParams p = plan_params(plan, dev_payload, nullptr);
+    std::memset(out, 0, sizeof *out);
+    out->ntiles = p.ntiles;
+    out->ngen = p.ngen;
+    out->nseg = p.nseg;
+    out->nconst = p.nconst;
+    out->general = p.general;
+    out->skip_z = p.skip_z;
+    out->num_cu = launch_cus(plan->ctx);
+    put_build(select_plan_build(p.ntiles, p.ngen, p.nseg, p.nconst, p.general, verify != 0, out->num_cu), &out->build);
+    return 0;
+}
+
+int crc32c_debug_packets_flags(const crc32c_packet *pkts, size_t npkts, int absolute, uint32_t *general_bits_out,
+                               int *needs_z_out) {
+    if (int rc = check_packets(pkts, npkts)) return rc;
+    HostPlan hp;
+    if (int rc = build_plan(pkts, npkts, &hp, absolute != 0)) return fail(rc, "invalid packet in batch");
+    if (general_bits_out) *general_bits_out = general_bits(hp);
+    if (needs_z_out) *needs_z_out = needs_z(hp) ? 1 : 0;
+    return 0;
+}
 
 int crc32c_chunks_dev(crc32c_ctx *ctx, const crc32c_packet *pkts, size_t npkts, const void *dev_payload,
                       uint32_t *dev_out, uint32_t flags, void *stream) {

@@ -106,6 +106,11 @@ constexpr Variant kVariants[] = {
     // (round 6) 83 (quarter units + early loads, general-tile code) with 8
     // waves per workgroup: one block off 16-byte alignment (an append)
     {95, "s4c_wg512_nt_quarter_nopad_early_prodgrid", 512, 1, true, true},
+    // the full-image general build (49) without the table staging: real
+    // lookups in whatever the LDS holds -- right only after a launch that left
+    // the full CRC32C image there, so not exact; the control of the cold-LDS
+    // tests (lds_poison.hip: after a poison it must be wrong)
+    {96, "s4_nt_nostage_prodgrid", 768, 1, false, true},
 };
 
 const Variant *find(int v) {
@@ -189,6 +194,7 @@ hipError_t launch_variant(const hdfs_crc::KParams &p, const Variant &v, uint32_t
     case 93: HDFS_LAUNCH(512, 2, kModeS4 | kModeNt | kModeS4C | kModeQuarter | kModeEarly); break;
     case 94: HDFS_LAUNCH(512, 2, kModeS4 | kModeNt | kModeS4C); break;
     case 95: HDFS_LAUNCH(512, 2, kS4Nt | kModeS4C | kModeNoPadT | kModeQuarter | kModeEarly); break;
+    case 96: HDFS_LAUNCH(768, 3, kS4Nt | kModeNoStage); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

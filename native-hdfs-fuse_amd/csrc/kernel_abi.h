@@ -5,6 +5,7 @@
 
 #include "crc_math.h"
 #include "plan.h"
+#include "plan_select.h"
 
 namespace hdfs_crc {
 
@@ -33,8 +34,6 @@ struct BlockRef {
 };
 // Blocks one launch carries (in the kernel arguments: 16 B each).
 constexpr uint32_t kMaxLaunchBlocks = 32;
-
-constexpr uint32_t kGeneralItems = 1u, kGeneralShift = 2u, kGeneralHalf = 4u, kGeneralPadded = 8u;  // KParams::general
 
 struct KParams {
     const FastTile *tiles;  // power-of-two and general tiles

@@ -410,8 +410,13 @@ void rebase_plan(HostPlan *plan, uint64_t *base) {
 
 extern "C" int crc32c_debug_plan(const crc32c_packet *pkts, size_t npkts, void *tiles, size_t tiles_cap, void *gen,
                                  size_t gen_cap, uint64_t *ntiles, uint64_t *ngen) {
+    return crc32c_debug_plan_abs(pkts, npkts, 0, tiles, tiles_cap, gen, gen_cap, ntiles, ngen);
+}
+
+extern "C" int crc32c_debug_plan_abs(const crc32c_packet *pkts, size_t npkts, int absolute, void *tiles,
+                                     size_t tiles_cap, void *gen, size_t gen_cap, uint64_t *ntiles, uint64_t *ngen) {
     hdfs_crc::HostPlan plan;
-    const int rc = hdfs_crc::build_plan(pkts, npkts, &plan);
+    const int rc = hdfs_crc::build_plan(pkts, npkts, &plan, absolute != 0);
     if (rc) return rc;
     if (ntiles) *ntiles = plan.tiles.size();
     if (ngen) *ngen = plan.gen.size();

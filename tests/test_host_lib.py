@@ -11,6 +11,7 @@ import re
 import numpy as np
 import pytest
 
+import cold_lds_cases
 import oracle
 from conftest import ROOT, golden_fill
 from kernel_model import KernelModel, KernelModelS4
@@ -43,7 +44,8 @@ def test_exports_every_declared_symbol(hdfs):
     dbg = _declared_functions(debug_only=True)
     assert dbg == {"crc32c_debug_plan_exec_variant", "crc32c_debug_variant_name", "crc32c_debug_stream_probe",
                    "crc32c_debug_resident_create", "crc32c_debug_resident_submit", "crc32c_debug_resident_wait",
-                   "crc32c_debug_resident_stats", "crc32c_debug_resident_trace", "crc32c_debug_resident_destroy"}
+                   "crc32c_debug_resident_stats", "crc32c_debug_resident_trace", "crc32c_debug_resident_destroy",
+                   "crc32c_debug_lds_poison", "crc32c_debug_lds_peek"}
     dlib = hdfs.debug_lib()
     for n in sorted(dbg):
         assert hasattr(dlib, n), n
@@ -654,3 +656,162 @@ def test_plan_keeps_stream_objects_alive():
     assert pkg._stream_handle(s, mp._streams) == 0x1234 and mp._streams == {0x1234: s}
     mp.close()
     assert mp._streams == {}
+
+
+# ---- the choice of production kernel build (csrc/plan_select.h) --------------------
+def _product_kernels(hdfs):
+    """(threads, waves per SIMD, mode) of every plan kernel in the product library."""
+    blob = open(hdfs.LIB_PATH, "rb").read()
+    return {tuple(int(x) for x in m) for m in
+            re.findall(rb"_Z23hdfs_crc32c_plan_kernelILi(\d+)ELi(\d+)ELi(\d+)EEvN8hdfs_crc7KParamsE", blob)}
+
+
+# The expected build, written out: rows are KParams::general (1 general tiles,
+# 2 shifted loads, 4 half tiles, 8 padded power-of-two tiles), columns the
+# batch-size band -- tiles per CU <= 2, <= 3, <= 6, then work items per CU
+# <= 16, then larger.  Half tiles and padded tiles never run in the
+# small-batch builds; half tiles win over everything else.
+_SMALL_BANDS = ("quarter_early", "quarter", "halves", "small")
+_BUILD_TABLE = {
+    0: ("one_block8", "quarter", "halves", "small", "bulk"),
+    1: _SMALL_BANDS + ("gitems",),
+    2: _SMALL_BANDS + ("shift",),
+    3: _SMALL_BANDS + ("both_hoist",),
+    4: ("half",) * 5, 5: ("half",) * 5, 6: ("half_shift",) * 5, 7: ("half_shift",) * 5,
+    8: ("both_hoist",) * 5, 9: ("both_hoist",) * 5, 10: ("both_hoist",) * 5, 11: ("both_hoist",) * 5,
+    12: ("half",) * 5, 13: ("half",) * 5, 14: ("half_shift",) * 5, 15: ("half_shift",) * 5,
+}
+_BAND_UNITS = (4, 4, 2, 1, 1)  # units per tile where the small-batch builds run
+
+
+def _band(ntiles: int, items: int, cu: int) -> int:
+    if items > 16 * cu:
+        return 4
+    return 0 if ntiles <= 2 * cu else 1 if ntiles <= 3 * cu else 2 if ntiles <= 6 * cu else 3
+
+
+def _select_sweep():
+    """(ntiles, ngen, nseg, nconst, num_cu) at every threshold of the launch path."""
+    for cu in (256, 64, 8, 1):
+        for k in (2, 3, 6):
+            for plus in (0, 1):
+                yield k * cu + plus, 0, 0, 0, cu
+        for plus in (0, 1):
+            yield 16 * cu + plus, 0, 0, 0, cu                      # work items: tiles ...
+            yield 0, 2 * (16 * cu + plus), 0, 0, cu                # ... gen items, two per work item ...
+            yield 0, 0, 2 * (16 * cu + plus) - 1, 0, cu            # ... seg items (an odd count rounds up) ...
+            yield 2 * cu, 0, 0, 14 * cu + plus, cu                 # ... few tiles and constant runs
+            yield 2 * cu, 2 * (7 * cu), 2 * (7 * cu + plus), 0, cu
+        yield 1, 0, 0, 0, cu
+        yield 0, 1, 0, 0, cu
+        yield 0, 0, 0, 5, cu   # constant runs only
+        yield 0, 0, 0, 0, cu   # nothing at all
+
+
+def test_select_build_at_every_threshold(hdfs):
+    """crc32c_debug_select_build -- the function launch_plan_kernel launches
+    from -- against the table above at the first and last batch size of every
+    build, for every `general` value, exec and verify, on 256, 64, 8 and 1
+    CUs; the grid is one workgroup per CU or per unit / item when there are
+    fewer, never 0; and the builds reachable are exactly the product
+    library's kernels."""
+    reached = set()
+    for ntiles, ngen, nseg, nconst, cu in _select_sweep():
+        items = ntiles + (ngen + 1) // 2 + (nseg + 1) // 2 + nconst
+        band = _band(ntiles, items, cu)
+        for general in range(16):
+            name = _BUILD_TABLE[general][band]
+            threads, wps, mode = cold_lds_cases.KERNELS[name]
+            units = _BAND_UNITS[band] if name in _SMALL_BANDS + ("one_block8",) else 1
+            grid = max(1, min(cu, items + (units - 1) * ntiles))
+            for verify in (False, True):
+                b = hdfs.debug_select_build(ntiles, ngen, nseg, nconst, general, verify, cu)
+                what = (ntiles, ngen, nseg, nconst, general, verify, cu, name)
+                assert b.kernel == (threads, wps, mode | (64 if verify else 0)), what
+                assert (b.units_per_tile, b.grid) == (units, grid), what
+                reached.add(b.kernel)
+    assert reached == _product_kernels(hdfs) and len(reached) == 22
+    with pytest.raises(hdfs.Crc32cError):
+        hdfs.debug_select_build(1, 0, 0, 0, 0, False, 0)
+
+
+def test_cold_lds_case_table_names_every_production_kernel(hdfs):
+    """The cold-LDS GPU cases name all 22 production kernels, and on 256 CUs
+    the launch-path predicates and the selector send each packet case to the
+    kernel, the `general` bits and the skip_z it names (the GPU test asserts
+    the same of the real plan on the real CU count)."""
+    assert cold_lds_cases.kernels_named() == _product_kernels(hdfs)
+    assert len({c.id for c in cold_lds_cases.CASES}) == len(cold_lds_cases.CASES)
+    for c in cold_lds_cases.CASES:
+        shape = cold_lds_cases.SHAPES[c.shape]
+        n = c.packets_at(256)
+        pk = cold_lds_cases.packets(shape, n)
+        assert int((pk["payload_off"] + pk["len"]).max()) + shape.ptr_off <= 33 << 20, c.id  # (the table tops at 32 MiB)
+        general, needs_z = hdfs.debug_packets_flags(pk)
+        if shape.ptr_off & 15:
+            general |= 2  # (plan_params: the payload pointer's own misalignment)
+        tiles, gen = hdfs.debug_plan(pk)
+        assert (general, int(not needs_z)) == (c.general, c.skip_z), c.id
+        for verify in (False, True):
+            b = hdfs.debug_select_build(tiles.size, gen.size, 0, 0, general, verify, 256)
+            t, w, m = cold_lds_cases.KERNELS[c.kernel]
+            assert b.kernel == (t, w, m | (64 if verify else 0)), (c.id, b.kernel)
+
+
+# ---- needs_z / the `general` bits against an independent reading of the items -------
+def _read_flags(tiles, gen):
+    """(general bits, needs Z) from the work items alone (csrc/plan.h meta encodings)."""
+    general, z = 0, gen.size > 0
+    padded_general = half = False
+    for t in tiles:
+        meta, src = int(t["meta"]), int(t["src"]) & ((1 << 48) - 1)
+        lg, pad = (meta >> 8) & 0xFF, (meta >> 18) & 511
+        if meta & 0x80000000:        # general tile
+            general |= 1
+            z = True
+            padded_general |= pad != 0
+        elif meta & 0x40000000:      # half tile (bits 8-15: M whole blocks per chunk)
+            general |= 1 | 4
+            half = True
+            z |= lg > 0
+        elif pad:                    # padded power-of-two tile
+            general |= 1 | 8
+            padded_general = True
+            z |= lg > 0
+        else:                        # power-of-two tile
+            z |= lg > 0
+            if src & 15:
+                general |= 2
+    if padded_general and not half:
+        general |= 2
+    return general, z
+
+
+def _z_cases():
+    for name, pk in _cases():
+        yield name, pk, None
+    # whole chunks only; needs Z: known by construction (None: whatever the items say)
+    for bpc, ln, z in ((256, 65536, False), (300, 65400, False), (512, 65536, False), (700, 65100, True),
+                       (1000, 65000, True), (1024, 65536, True), (1536, 64512, True), (8192, 65536, True)):
+        for off in (4160, 4165):
+            pk = oracle.uniform_packets(3, pkt_len=ln, bpc=bpc, stride=1 << 17)
+            pk["payload_off"] += off
+            yield "bpc%d_off%d" % (bpc, off), pk, z
+        pk = oracle.uniform_packets(3, pkt_len=ln, bpc=bpc, stride=1 << 17)
+        pk["payload_off"] += 4096 + 5  # (absolute: a padded chunk's early loads would leave its 4 KiB page)
+        yield "bpc%d_page_start" % bpc, pk, None
+
+
+@pytest.mark.parametrize("name,pk,z", list(_z_cases()), ids=[c[0] for c in _z_cases()])
+@pytest.mark.parametrize("absolute", [False, True], ids=["relative", "absolute"])
+def test_needs_z_and_general_bits_match_the_items(hdfs, name, pk, z, absolute):
+    """needs_z and the predicates behind KParams::general (static in
+    crc32c_runtime.hip, through crc32c_debug_packets_flags) against a reading
+    of the plan's items written here: Z is needed iff there is a gen item, a
+    general tile, a half tile with M > 0, or a power-of-two / padded tile with
+    lg > 0."""
+    tiles, gen = hdfs.debug_plan(pk, absolute)
+    want = _read_flags(tiles, gen)
+    assert hdfs.debug_packets_flags(pk, absolute) == want, name
+    if z is not None:
+        assert gen.size == 0 and want[1] == z, name
