@@ -531,6 +531,70 @@ size_t crc32c_frame_packets(const crc32c_packet *pkts, size_t npkts, const uint3
  * wire order with CRC32C_BIG_ENDIAN). */
 void crc32c_block_md5(const uint32_t *sums, size_t n, uint32_t flags, uint8_t md5[16]);
 
+/* ---------------------------------------------------------------------------
+ * 6b. Block MD5-of-CRCs on the GPU, and the MD5MD5CRC file checksum.
+ *
+ * crc32c_block_md5 for many blocks at once, over checksum arrays that are
+ * already in device memory -- what crc32c_plan_exec, crc32c_plan_exec_blocks
+ * and (after the join) crc32c_multi_plan_exec's root_out leave there -- so
+ * nothing is copied back before the MD5.  MD5 is one serial chain per
+ * message: the kernel runs one lane per block, 64 blocks per wave.  One
+ * block alone is therefore SLOWER than crc32c_block_md5 on the host; the
+ * time of a launch barely grows with its block count until the device is
+ * full.  crc32c_block_md5 remains the path for a handful of blocks
+ * (measured, 8192 checksums per block: one launch 0.34-0.40 ms for 1 to 8192
+ * blocks, the host 49 us per block, the GPU call faster from 16 blocks up;
+ * INTEGRATION.md, "Block MD5-of-CRCs").
+ *
+ * Block i's 16 digest bytes go to dev_md5 + 16 i in RFC 1321 order (what
+ * crc32c_block_md5 writes).  flags: only CRC32C_BIG_ENDIAN, the order the
+ * checksums are STORED in, as in crc32c_block_md5 (0 = host order; with the
+ * flag = wire order, as a CRC32C_BIG_ENDIAN plan stores them); the digest is
+ * the same either way.  Every device pointer (checksum arrays, dev_md5) must
+ * be 4-byte aligned and needs no more than that; an array is read up to its
+ * last checksum and not a byte further, so it may end where an allocation
+ * ends.  The three device calls are asynchronous on `stream` (a hipStream_t,
+ * NULL = the default stream), keep no host-side state and may be captured
+ * into a HIP graph.  They return -EINVAL (crc32c_last_error says why) and
+ * launch nothing for: any other flag bit, ctx == NULL, crc_per_block == 0
+ * with nsums > 0, a NULL array with checksums in it, dev_md5 == NULL, a NULL
+ * output pointer where blocks exist, a pointer off 4-byte alignment.
+ * nsums == 0 / nblocks == 0: 0, nothing written.
+ *
+ * crc32c_md5_blocks: the blocks of one contiguous array, block i =
+ * dev_sums[i * crc_per_block ...), the last one ragged;
+ * crc32c_md5_nblocks(nsums, crc_per_block) digests.  ONE launch for any
+ * block count, no table.
+ *
+ * crc32c_md5_block_list: blocks anywhere in device memory.  dev_sums and
+ * nsums are HOST arrays of nblocks entries, consumed before the call
+ * returns; an entry with nsums[i] == 0 may be NULL and gets the MD5 of the
+ * empty message.  The references ride in the kernel arguments (as
+ * crc32c_plan_exec_blocks' block table does): one launch per
+ * CRC32C_MD5_LIST_MAX_BLOCKS blocks.  Launches on one stream run one after
+ * another and each takes about as long as one block's chain, so a large
+ * scattered set costs nblocks / CRC32C_MD5_LIST_MAX_BLOCKS of them back to
+ * back: lay such a set out contiguously and use crc32c_md5_blocks.
+ *
+ * crc32c_plan_exec_blocks_md5: crc32c_plan_exec_blocks(plan, dev_payloads,
+ * dev_outs, nblocks, stream), then the MD5 of each block's
+ * crc32c_plan_nchecksums(plan) checksums at dev_outs[i] on the same stream
+ * (list form); the stored order is the plan's (its CRC32C_BIG_ENDIAN flag).
+ *
+ * crc32c_file_md5 (host): MD5 over the nblocks block digests back to back
+ * (16 nblocks bytes) = the digest of Hadoop's MD5-of-MD5-of-CRC file
+ * checksum (MD5MD5CRC32FileChecksum).
+ * ------------------------------------------------------------------------- */
+#define CRC32C_MD5_LIST_MAX_BLOCKS 256u
+uint64_t crc32c_md5_nblocks(uint64_t nsums, uint32_t crc_per_block);
+int crc32c_md5_blocks(crc32c_ctx *ctx, const uint32_t *dev_sums, uint64_t nsums, uint32_t crc_per_block,
+                      uint32_t flags, uint8_t *dev_md5, void *stream);
+int crc32c_md5_block_list(crc32c_ctx *ctx, const uint32_t *const *dev_sums, const uint32_t *nsums, size_t nblocks,
+                          uint32_t flags, uint8_t *dev_md5, void *stream);
+int crc32c_plan_exec_blocks_md5(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs,
+                                size_t nblocks, uint8_t *dev_md5, void *stream);
+void crc32c_file_md5(const uint8_t *block_md5s, size_t nblocks, uint8_t md5[16]);
+
 /* The read side ("next" row 1): the packet stream a DataNode sends for
  * OP_READ_BLOCK with sendChecksums, per packet PLEN (u32 BE) | HLEN (u16 BE)
  * | PacketHeaderProto | checksums (u32 BE) | data (hadoop_rpc_receive_packets,

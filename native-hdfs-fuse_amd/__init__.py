@@ -241,6 +241,11 @@ def _bind(L):
         "crc32c_plan_verify_bitmap": (i32, [vp, vp, vp, vp, vp, vp]),
         "crc32c_frame_packets": (sz, [vp, sz, vp, u32, u64, ctypes.c_int64, u32, vp, sz, vp]),
         "crc32c_block_md5": (None, [vp, sz, u32, vp]),
+        "crc32c_md5_nblocks": (u64, [u64, u32]),
+        "crc32c_md5_blocks": (i32, [vp, vp, u64, u32, u32, vp, vp]),
+        "crc32c_md5_block_list": (i32, [vp, vp, vp, sz, u32, vp, vp]),
+        "crc32c_plan_exec_blocks_md5": (i32, [vp, vp, vp, sz, vp, vp]),
+        "crc32c_file_md5": (None, [vp, sz, vp]),
         "crc32c_verify_host": (ctypes.c_int64, [vp, vp, vp, sz, vp, u32, vp]),
         "crc32c_debug_affine_constants": (None, [u32, vp, vp]),
         "hdfs_crc32": (u32, [u32, vp, sz]),
@@ -352,6 +357,26 @@ def block_md5(sums: np.ndarray, flags: int = 0) -> bytes:
     return md5.tobytes()
 
 
+MD5_LIST_MAX_BLOCKS = 256  # CRC32C_MD5_LIST_MAX_BLOCKS: blocks per launch of Context.md5_block_list
+
+
+def md5_nblocks(nsums: int, crc_per_block: int) -> int:
+    """Blocks (digests) of a contiguous checksum array cut every crc_per_block checksums."""
+    return int(lib().crc32c_md5_nblocks(nsums, crc_per_block))
+
+
+def file_md5(block_md5s) -> bytes:
+    """crc32c_file_md5: MD5 over the concatenated 16-byte block digests (bytes, or a
+    uint8 array of 16 n bytes) = Hadoop's MD5-of-MD5-of-CRC file checksum."""
+    a = np.frombuffer(bytes(block_md5s), np.uint8) if not isinstance(block_md5s, np.ndarray) else block_md5s
+    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    if a.size % 16:
+        raise ValueError("block digests are 16 bytes each (%d bytes given)" % a.size)
+    md5 = np.zeros(16, np.uint8)
+    lib().crc32c_file_md5(_np_ptr(a) if a.size else None, a.size // 16, _np_ptr(md5))
+    return md5.tobytes()
+
+
 def nchunks(length: int, bpc: int) -> int:
     return int(lib().crc32c_nchunks(length, bpc))
 
@@ -435,6 +460,26 @@ class Context:
         _check(lib().crc32c_chunks_dev(self.handle, _np_ptr(pkts), pkts.size, ctypes.c_void_p(dev_payload),
                                        ctypes.c_void_p(dev_out), flags, ctypes.c_void_p(stream)), "crc32c_chunks_dev")
 
+    def md5_blocks(self, dev_sums: int, nsums: int, crc_per_block: int, dev_md5: int, flags: int = 0,
+                   stream=0) -> None:
+        """crc32c_md5_blocks: the MD5 of every crc_per_block checksums of a contiguous device array
+        (the last block ragged), 16 bytes each to dev_md5; one launch, asynchronous on ``stream``.
+        ``flags``: CRC32C_BIG_ENDIAN when the checksums are stored in wire order."""
+        _check(lib().crc32c_md5_blocks(self.handle, ctypes.c_void_p(dev_sums), nsums, crc_per_block, flags,
+                                       ctypes.c_void_p(dev_md5), ctypes.c_void_p(_stream_handle(stream, {}))),
+               "crc32c_md5_blocks")
+
+    def md5_block_list(self, dev_sums, nsums, dev_md5: int, flags: int = 0, stream=0) -> None:
+        """crc32c_md5_block_list: the MD5 of nsums[i] checksums at device address dev_sums[i] (0 allowed
+        where nsums[i] == 0) to dev_md5 + 16 i; one launch per MD5_LIST_MAX_BLOCKS blocks."""
+        n = len(dev_sums)
+        if len(nsums) != n:
+            raise ValueError("dev_sums and nsums differ in length")
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(int(x)) for x in dev_sums])
+        counts = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in nsums])
+        _check(lib().crc32c_md5_block_list(self.handle, ptrs, counts, n, flags, ctypes.c_void_p(dev_md5),
+                                           ctypes.c_void_p(_stream_handle(stream, {}))), "crc32c_md5_block_list")
+
 
 class Plan:
     """Device-resident batch plan (crc32c_plan): build once, execute many.
@@ -494,6 +539,16 @@ class Plan:
         outs = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_outs])
         _check(lib().crc32c_plan_exec_blocks(self.handle, pays, outs, n, ctypes.c_void_p(stream)),
                "crc32c_plan_exec_blocks")
+
+    def exec_blocks_md5(self, dev_payloads, dev_outs, dev_md5: int, stream=0) -> None:
+        """crc32c_plan_exec_blocks_md5: exec_blocks, then each block's MD5 (16 bytes to dev_md5 + 16 i)
+        on the same stream; the checksums' stored order is the plan's."""
+        stream = self._stream(stream)
+        n = len(dev_payloads)
+        pays = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_payloads])
+        outs = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_outs])
+        _check(lib().crc32c_plan_exec_blocks_md5(self.handle, pays, outs, n, ctypes.c_void_p(dev_md5),
+                                                 ctypes.c_void_p(stream)), "crc32c_plan_exec_blocks_md5")
 
     def blocks(self, max_blocks: int = 16, window_us: int = 20, resident: bool = False,
                idle_us: int = 0) -> "Blocks":

@@ -179,3 +179,14 @@ extern "C" void crc32c_block_md5(const uint32_t *sums, size_t n, uint32_t flags,
     }
     m.finish(md5);
 }
+
+extern "C" uint64_t crc32c_md5_nblocks(uint64_t nsums, uint32_t crc_per_block) {
+    if (!crc_per_block) return 0;
+    return nsums / crc_per_block + (nsums % crc_per_block ? 1 : 0);
+}
+
+extern "C" void crc32c_file_md5(const uint8_t *block_md5s, size_t nblocks, uint8_t md5[16]) {
+    Md5 m;
+    if (nblocks) m.update(block_md5s, 16 * nblocks);
+    m.finish(md5);
+}

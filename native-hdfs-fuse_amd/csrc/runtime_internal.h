@@ -225,6 +225,8 @@ void plan_forget_stream(crc32c_plan *plan, hipStream_t stream);
 // crc32c_plan_exec_blocks; `stop` (optional) is completed by the last launch.
 int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs, size_t nblocks,
                 hipStream_t stream, hipEvent_t stop);
+// Loads the block-MD5 kernels' code object onto the current device (crc32c_md5.hip).
+hipError_t preload_md5_kernels();
 // A destroyed plan's blocks back to the pools once its launches are done.
 void release_plan_blocks(crc32c_plan *plan);
 // Context teardown: waits for the releases, frees every pooled block.

@@ -4,7 +4,10 @@ kind (the GPU fuzz test's generator, plus CRC32 and wire-order flags and a
 batch size that selects each kernel build) and random FUSE-shaped
 buffer-list write plans (NULL zero fill, chunks spanning buffers), each
 executed on one of two streams and verified with a mismatch bitmap against
-k random flipped checksums, every result checked against the oracle.
+k random flipped checksums, every result checked against the oracle; about
+a third of the batches also get the block MD5 of every cpb checksums
+(crc32c_md5_blocks, a random cpb) straight from the exec's output on its
+stream, checked against hashlib.
 Writes a progress line every ~10 s (and the summary at the end) to --out.
 
     python tools/soak.py [--seconds 300] [--out gpurun_out/soak.jsonl]
@@ -12,6 +15,7 @@ Writes a progress line every ~10 s (and the summary at the end) to --out.
 from __future__ import annotations
 
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -128,6 +132,7 @@ def main():
     stats = {"batches": 0, "checksums": 0, "bytes": 0, "mismatching_results": 0, "verify_bits_checked": 0}
     t0 = last = time.time()
     stats["write_plans"] = 0
+    stats["md5_blocks"] = 0
     while time.time() - t0 < args.seconds:
         if rng.random() < 0.3:  # a FUSE-shaped buffer-list write plan
             ok, n, nbytes = write_round(torch, hdfs, orc, ctx, rng, streams[int(rng.integers(0, 2))])
@@ -160,6 +165,13 @@ def main():
         plan = hdfs.Plan(ctx, pk, flags)
         s.wait_stream(torch.cuda.current_stream())  # (the payload's copy, out's fill)
         plan.exec(dev.data_ptr(), out.data_ptr(), s.cuda_stream)
+        # every third batch or so: the MD5 of every cpb checksums straight from the exec's output,
+        # on its stream (crc32c_md5_blocks; a random cpb, so ragged last blocks and every padding form)
+        md5_cpb = int(rng.integers(1, 300)) if rng.random() < 0.35 else 0
+        if md5_cpb:
+            d_md5 = torch.zeros(16 * hdfs.md5_nblocks(n, md5_cpb), dtype=torch.uint8, device="cuda")
+            s.wait_stream(torch.cuda.current_stream())  # (d_md5's fill)
+            ctx.md5_blocks(out.data_ptr(), n, md5_cpb, d_md5.data_ptr(), flags & hdfs.CRC32C_BIG_ENDIAN, s.cuda_stream)
         flips = sorted(set(int(x) for x in rng.integers(0, n, int(rng.integers(0, 6)))))
         exp = want.copy()
         for i in flips:
@@ -176,6 +188,11 @@ def main():
         b = np.unpackbits(bits.cpu().numpy().view(np.uint8), bitorder="little")
         ok = (np.array_equal(got, want) and r == [len(flips), flips[0] if flips else 0xFFFFFFFF]
               and np.flatnonzero(b).tolist() == flips)
+        if md5_cpb:
+            wire = want if flags & hdfs.CRC32C_BIG_ENDIAN else want.byteswap()  # (big-endian bytes in memory)
+            md5_want = b"".join(hashlib.md5(wire[i:i + md5_cpb].tobytes()).digest() for i in range(0, n, md5_cpb))
+            ok = ok and d_md5.cpu().numpy().tobytes() == md5_want
+            stats["md5_blocks"] += len(md5_want) // 16
         plan.close()
         stats["batches"] += 1
         stats["checksums"] += n
