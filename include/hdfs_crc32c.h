@@ -595,6 +595,93 @@ int crc32c_plan_exec_blocks_md5(crc32c_plan *plan, const void *const *dev_payloa
                                 size_t nblocks, uint8_t *dev_md5, void *stream);
 void crc32c_file_md5(const uint8_t *block_md5s, size_t nblocks, uint8_t md5[16]);
 
+/* ---------------------------------------------------------------------------
+ * 6c. Composite CRCs: a block's and a file's CRC from the chunk checksums
+ * (Hadoop's COMPOSITE_CRC block checksum type and its COMPOSITE-CRC32C /
+ * COMPOSITE-CRC32 file checksum).
+ *
+ * The MD5 of section 6b hashes the chunk checksums, so it depends on
+ * bytes-per-checksum and on the block size.  The composite does not: chunk
+ * CRCs combine algebraically into the CRC of the bytes they cover,
+ *     crc(A || B) = crc(A) * x^(8 |B|) ^ crc(B)   in GF(2)[x] mod P,
+ * with crc(empty) = 0.  A block's composite therefore EQUALS crc32c(0, data,
+ * len) over the block's bytes (crc32 for CRC32C_TYPE_CRC32) whatever bpc,
+ * packet size or block size the checksums were made with, and a file's equals
+ * the CRC of the file's bytes.  In a run of chunks only the lengths of the
+ * chunks AFTER the first enter: a cell whose chunks are [any <= bpc], bpc,
+ * ..., bpc, [last_len <= bpc] needs bpc and last_len, nothing else.
+ *
+ * Host:
+ * crc32c_combine(crc_a, crc_b, len_b, flags): the CRC of A || B from crc(A),
+ * crc(B) and |B|, in O(log len_b) 32-step products.  flags: only
+ * CRC32C_TYPE_CRC32 (the polynomial; other bits are ignored).  len_b == 0
+ * gives crc_a ^ crc_b (crc_b is then crc(empty) = 0: crc_a).
+ * crc32c_block_composite(sums, n, bpc, last_len, flags, &crc): n chunk
+ * checksums -> the CRC of their bytes, in host order; every chunk after the
+ * first covers bpc bytes, the last one last_len (1..bpc; with n == 1 it is
+ * not used beyond that check).  flags: CRC32C_BIG_ENDIAN (how sums are
+ * STORED) and CRC32C_TYPE_CRC32.  n == 0 gives 0.  -EINVAL: bpc == 0, with
+ * n > 0 last_len == 0 or > bpc or sums == NULL, crc == NULL, another flag.
+ * The path for a handful of blocks (about 2.5 ns per checksum).
+ * crc32c_file_composite(block_crcs, block_lens, nblocks, flags, &crc): block
+ * CRCs in HOST order combined by the blocks' byte lengths (a zero-length
+ * block has CRC 0 and changes nothing).  flags: only CRC32C_TYPE_CRC32.  The
+ * result is the VALUE of Hadoop's COMPOSITE-CRC32C (COMPOSITE-CRC32) file
+ * checksum; its wire form (CompositeCrcFileChecksum's bytes) is that value
+ * as 4 big-endian bytes.
+ *
+ * Device (as section 6b's calls: asynchronous on `stream`, no host-side
+ * state, capturable into a HIP graph; every device pointer 4-byte aligned
+ * and no more; an array is read up to its last checksum and not a byte
+ * further; bad arguments return -EINVAL with a crc32c_last_error text and
+ * launch nothing).  flags: CRC32C_TYPE_CRC32 and CRC32C_BIG_ENDIAN -- the
+ * order the input checksums are stored in AND the order the outputs are
+ * stored in, so a big-endian output array is the response's blockChecksum
+ * bytes.  The kernel runs one wave per 8192 checksums of a cell: lanes run
+ * Horner's rule with x^(8 bpc 64) from a table in LDS, merge pairwise, and a
+ * cell of more than 8193 checksums is split over waves and workgroups whose
+ * weighted values are xor-ed into the output (which the call then clears on
+ * the stream first).
+ *
+ * crc32c_composite_cells: cell i = dev_sums[i * crc_per_cell ...), the last
+ * cell ragged; every checksum covers bpc bytes but the array's very last one
+ * (last_len, 1..bpc).  One u32 per cell to dev_crcs[i];
+ * crc32c_md5_nblocks(nsums, crc_per_cell) of them.  ONE launch for any cell
+ * count.  Serves a file's blocks (cell = block) and striped reads
+ * (stripeLength = crc_per_cell * bpc).  nsums == 0: 0, nothing written.
+ * crc32c_composite_block_list: blocks anywhere in device memory; dev_sums,
+ * nsums and last_lens are HOST arrays of nblocks entries, consumed before the
+ * call returns.  The references and each block's x^(8 last_len) ride in the
+ * kernel arguments (16 bytes per block): one launch per
+ * CRC32C_COMPOSITE_LIST_MAX_BLOCKS blocks.  An entry with nsums[i] == 0 may
+ * be NULL (its last_len is not looked at) and yields 0.
+ * crc32c_plan_exec_blocks_composite: crc32c_plan_exec_blocks, then the list
+ * form over its outputs on the same stream; polynomial and stored order are
+ * the plan's.  The plan's chunks must have the composite shape: in checksum
+ * order from index 0 without gaps, [<= bpc], bpc, ..., bpc, [last_len] under
+ * one bpc (zero-length packets ignored) -- uniform plans, a ragged last
+ * packet, crc32c_plan_create_buffers plans with an unaligned blockoffset.
+ * crc32c_plan_composite_shape(plan, &bpc, &last_len) tells (0, or -EINVAL
+ * for mixed bpc, gaps, a short packet in the middle, an empty plan); with it
+ * crc32c_plan_exec + crc32c_composite_cells do the same for one plan.  A
+ * plan not of the shape gets -EINVAL from crc32c_plan_exec_blocks_composite
+ * and is otherwise unaffected.
+ * ------------------------------------------------------------------------- */
+#define CRC32C_COMPOSITE_LIST_MAX_BLOCKS 240u
+uint32_t crc32c_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t flags);
+int crc32c_block_composite(const uint32_t *sums, size_t n, uint32_t bpc, uint32_t last_len, uint32_t flags,
+                           uint32_t *crc);
+int crc32c_file_composite(const uint32_t *block_crcs, const uint64_t *block_lens, size_t nblocks, uint32_t flags,
+                          uint32_t *crc);
+int crc32c_composite_cells(crc32c_ctx *ctx, const uint32_t *dev_sums, uint64_t nsums, uint32_t crc_per_cell,
+                           uint32_t bpc, uint32_t last_len, uint32_t flags, uint32_t *dev_crcs, void *stream);
+int crc32c_composite_block_list(crc32c_ctx *ctx, const uint32_t *const *dev_sums, const uint32_t *nsums,
+                                const uint32_t *last_lens, size_t nblocks, uint32_t bpc, uint32_t flags,
+                                uint32_t *dev_crcs, void *stream);
+int crc32c_plan_exec_blocks_composite(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs,
+                                      size_t nblocks, uint32_t *dev_crcs, void *stream);
+int crc32c_plan_composite_shape(const crc32c_plan *plan, uint32_t *bpc, uint32_t *last_len);
+
 /* The read side ("next" row 1): the packet stream a DataNode sends for
  * OP_READ_BLOCK with sendChecksums, per packet PLEN (u32 BE) | HLEN (u16 BE)
  * | PacketHeaderProto | checksums (u32 BE) | data (hadoop_rpc_receive_packets,

@@ -110,6 +110,23 @@ int crc32c_debug_plan_launch_info(const crc32c_plan *plan, const void *dev_paylo
 int crc32c_debug_packets_flags(const crc32c_packet *pkts, size_t npkts, int absolute, uint32_t *general_bits,
                                int *needs_z);
 
+/* The composite-CRC kernel's geometry (csrc/crc32c_composite.hip; host only,
+ * no GPU): one wave combines a segment of up to run * lanes checksums, each
+ * lane up to `run` of them; a workgroup is waves_per_workgroup waves; a cell
+ * of MORE than split_above checksums (run * lanes + 1: the last checksum is
+ * outside the lanes' sums) is split over several waves, past
+ * waves_per_workgroup * run * lanes + 1 over several workgroups, whose values
+ * are xor-ed into a cleared output.  The tests place their sizes from these. */
+typedef struct crc32c_debug_composite_geom {
+    uint32_t run, lanes, waves_per_workgroup, split_above;
+} crc32c_debug_composite_geom;
+void crc32c_debug_composite_geometry(crc32c_debug_composite_geom *out);
+
+/* The composite shape crc32c_plan_create would record for a packet batch
+ * (hdfs_crc32c.h section 6c, crc32c_plan_composite_shape): 0 with *bpc /
+ * *last_len, or -EINVAL when the batch is not of the shape.  No GPU. */
+int crc32c_debug_packets_composite_shape(const crc32c_packet *pkts, size_t npkts, uint32_t *bpc, uint32_t *last_len);
+
 /* ---- 2. libhdfs_crc32c_debug.so only ---- */
 
 /* Launch of a plan with an explicit kernel variant (0 = production; see

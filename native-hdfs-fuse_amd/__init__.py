@@ -246,6 +246,15 @@ def _bind(L):
         "crc32c_md5_block_list": (i32, [vp, vp, vp, sz, u32, vp, vp]),
         "crc32c_plan_exec_blocks_md5": (i32, [vp, vp, vp, sz, vp, vp]),
         "crc32c_file_md5": (None, [vp, sz, vp]),
+        "crc32c_combine": (u32, [u32, u32, u64, u32]),
+        "crc32c_block_composite": (i32, [vp, sz, u32, u32, u32, vp]),
+        "crc32c_file_composite": (i32, [vp, vp, sz, u32, vp]),
+        "crc32c_composite_cells": (i32, [vp, vp, u64, u32, u32, u32, u32, vp, vp]),
+        "crc32c_composite_block_list": (i32, [vp, vp, vp, vp, sz, u32, u32, vp, vp]),
+        "crc32c_plan_exec_blocks_composite": (i32, [vp, vp, vp, sz, vp, vp]),
+        "crc32c_plan_composite_shape": (i32, [vp, vp, vp]),
+        "crc32c_debug_composite_geometry": (None, [vp]),
+        "crc32c_debug_packets_composite_shape": (i32, [vp, sz, vp, vp]),
         "crc32c_verify_host": (ctypes.c_int64, [vp, vp, vp, sz, vp, u32, vp]),
         "crc32c_debug_affine_constants": (None, [u32, vp, vp]),
         "hdfs_crc32": (u32, [u32, vp, sz]),
@@ -377,6 +386,55 @@ def file_md5(block_md5s) -> bytes:
     return md5.tobytes()
 
 
+COMPOSITE_LIST_MAX_BLOCKS = 240  # CRC32C_COMPOSITE_LIST_MAX_BLOCKS: blocks per launch of Context.composite_block_list
+
+
+def combine(crc_a: int, crc_b: int, len_b: int, flags: int = 0) -> int:
+    """crc32c_combine: the CRC of A || B from crc(A), crc(B) and len(B) (flags: CRC32C_TYPE_CRC32)."""
+    return int(lib().crc32c_combine(crc_a & 0xFFFFFFFF, crc_b & 0xFFFFFFFF, len_b, flags))
+
+
+def block_composite(sums: np.ndarray, bpc: int, last_len: int, flags: int = 0) -> int:
+    """crc32c_block_composite: chunk checksums (stored in host order, or wire order with
+    CRC32C_BIG_ENDIAN) -> the CRC of the bytes they cover; every chunk after the first is bpc bytes
+    long, the last one last_len."""
+    sums = np.ascontiguousarray(sums, dtype=np.uint32)
+    crc = ctypes.c_uint32(0)
+    _check(lib().crc32c_block_composite(_np_ptr(sums) if sums.size else None, sums.size, bpc, last_len, flags,
+                                        ctypes.byref(crc)), "crc32c_block_composite")
+    return int(crc.value)
+
+
+def file_composite(block_crcs, block_lens, flags: int = 0) -> int:
+    """crc32c_file_composite: block CRCs (host order) combined by the blocks' byte lengths = the
+    value of Hadoop's COMPOSITE-CRC32C / COMPOSITE-CRC32 file checksum (wire form: 4 big-endian bytes)."""
+    crcs = np.ascontiguousarray(block_crcs, dtype=np.uint32).reshape(-1)
+    lens = np.ascontiguousarray(block_lens, dtype=np.uint64).reshape(-1)
+    if crcs.size != lens.size:
+        raise ValueError("block_crcs and block_lens differ in length")
+    crc = ctypes.c_uint32(0)
+    _check(lib().crc32c_file_composite(_np_ptr(crcs) if crcs.size else None, _np_ptr(lens) if lens.size else None,
+                                       crcs.size, flags, ctypes.byref(crc)), "crc32c_file_composite")
+    return int(crc.value)
+
+
+def debug_composite_geometry() -> dict:
+    """crc32c_debug_composite_geometry: the composite kernel's run, lanes, waves_per_workgroup, split_above."""
+    g = np.zeros(4, np.uint32)
+    lib().crc32c_debug_composite_geometry(_np_ptr(g))
+    return dict(zip(["run", "lanes", "waves_per_workgroup", "split_above"], (int(x) for x in g)))
+
+
+def debug_packets_composite_shape(pkts):
+    """The (bpc, last_len) crc32c_plan_create would record for the batch, or None when it is not of the
+    composite shape (no GPU)."""
+    pkts = as_packets(pkts)
+    bpc, last = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    rc = lib().crc32c_debug_packets_composite_shape(_np_ptr(pkts) if pkts.size else None, pkts.size,
+                                                    ctypes.byref(bpc), ctypes.byref(last))
+    return None if rc else (int(bpc.value), int(last.value))
+
+
 def nchunks(length: int, bpc: int) -> int:
     return int(lib().crc32c_nchunks(length, bpc))
 
@@ -480,6 +538,32 @@ class Context:
         _check(lib().crc32c_md5_block_list(self.handle, ptrs, counts, n, flags, ctypes.c_void_p(dev_md5),
                                            ctypes.c_void_p(_stream_handle(stream, {}))), "crc32c_md5_block_list")
 
+    def composite_cells(self, dev_sums: int, nsums: int, crc_per_cell: int, bpc: int, last_len: int,
+                        dev_crcs: int, flags: int = 0, stream=0) -> None:
+        """crc32c_composite_cells: the CRC of the bytes behind every crc_per_cell checksums of a
+        contiguous device array (the last cell ragged; the array's last checksum covers last_len bytes),
+        one u32 each to dev_crcs; asynchronous on ``stream``.  ``flags``: CRC32C_BIG_ENDIAN (stored order
+        of inputs and outputs), CRC32C_TYPE_CRC32."""
+        _check(lib().crc32c_composite_cells(self.handle, ctypes.c_void_p(dev_sums), nsums, crc_per_cell, bpc,
+                                            last_len, flags, ctypes.c_void_p(dev_crcs),
+                                            ctypes.c_void_p(_stream_handle(stream, {}))), "crc32c_composite_cells")
+
+    def composite_block_list(self, dev_sums, nsums, last_lens, bpc: int, dev_crcs: int, flags: int = 0,
+                             stream=0) -> None:
+        """crc32c_composite_block_list: the composite CRC of nsums[i] checksums at device address
+        dev_sums[i] (0 allowed where nsums[i] == 0), last chunk last_lens[i] bytes, to dev_crcs[i]; one
+        launch per COMPOSITE_LIST_MAX_BLOCKS blocks."""
+        n = len(dev_sums)
+        if len(nsums) != n or len(last_lens) != n:
+            raise ValueError("dev_sums, nsums and last_lens differ in length")
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(int(x)) for x in dev_sums])
+        counts = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in nsums])
+        lasts = (ctypes.c_uint32 * max(n, 1))(*[int(x) for x in last_lens])
+        _check(lib().crc32c_composite_block_list(self.handle, ptrs, counts, lasts, n, bpc, flags,
+                                                 ctypes.c_void_p(dev_crcs),
+                                                 ctypes.c_void_p(_stream_handle(stream, {}))),
+               "crc32c_composite_block_list")
+
 
 class Plan:
     """Device-resident batch plan (crc32c_plan): build once, execute many.
@@ -549,6 +633,25 @@ class Plan:
         outs = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_outs])
         _check(lib().crc32c_plan_exec_blocks_md5(self.handle, pays, outs, n, ctypes.c_void_p(dev_md5),
                                                  ctypes.c_void_p(stream)), "crc32c_plan_exec_blocks_md5")
+
+    def exec_blocks_composite(self, dev_payloads, dev_outs, dev_crcs: int, stream=0) -> None:
+        """crc32c_plan_exec_blocks_composite: exec_blocks, then each block's composite CRC (one u32 to
+        dev_crcs[i], stored in the plan's order) on the same stream; the plan must have the composite
+        shape (composite_shape)."""
+        stream = self._stream(stream)
+        n = len(dev_payloads)
+        pays = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_payloads])
+        outs = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_outs])
+        _check(lib().crc32c_plan_exec_blocks_composite(self.handle, pays, outs, n, ctypes.c_void_p(dev_crcs),
+                                                       ctypes.c_void_p(stream)), "crc32c_plan_exec_blocks_composite")
+
+    def composite_shape(self):
+        """crc32c_plan_composite_shape: (bpc, last_len) when the plan's checksums combine into the CRC of
+        its bytes with these two lengths; Crc32cError(-EINVAL) otherwise."""
+        bpc, last = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib().crc32c_plan_composite_shape(self.handle, ctypes.byref(bpc), ctypes.byref(last)),
+               "crc32c_plan_composite_shape")
+        return int(bpc.value), int(last.value)
 
     def blocks(self, max_blocks: int = 16, window_us: int = 20, resident: bool = False,
                idle_us: int = 0) -> "Blocks":

@@ -912,6 +912,8 @@ int make_plan(crc32c_ctx *ctx, const HostPlan &hp, uint32_t flags, bool absolute
     ctx->refs.fetch_add(1, std::memory_order_relaxed);  // (released by crc32c_plan_destroy)
     p->nchecksums = hp.nchecksums;
     p->payload_bytes = hp.payload_bytes;
+    p->comp_bpc = hp.comp_bpc;
+    p->comp_last = hp.comp_last;
     p->flags = flags & (CRC32C_BIG_ENDIAN | CRC32C_TYPE_CRC32);
     p->counted = (flags & CRC32C_COUNT_COMPLETION) != 0;
     p->abs_base = abs_base;
@@ -964,6 +966,7 @@ int crc32c_ctx_create(int device, crc32c_ctx **out) {
     c->num_cu = prop.multiProcessorCount;
     HIP_TRY(preload_plan_kernels());
     HIP_TRY(preload_md5_kernels());
+    HIP_TRY(preload_composite_kernels());
     c->host_pool.pinned = true;
     HIP_TRY(hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking));
     for (int ty = 0; ty < 2; ++ty) {
@@ -1259,6 +1262,15 @@ int crc32c_plan_destroy(crc32c_plan *plan) {
 }
 
 uint64_t crc32c_plan_nchecksums(const crc32c_plan *plan) { return plan ? plan->nchecksums : 0; }
+
+int crc32c_plan_composite_shape(const crc32c_plan *plan, uint32_t *bpc, uint32_t *last_len) {
+    if (!plan) return fail(-EINVAL, "plan == NULL");
+    if (!plan->comp_bpc)
+        return fail(-EINVAL, "the plan's chunks are not [<= bpc], bpc, ..., bpc, [last_len] from checksum 0 without gaps");
+    if (bpc) *bpc = plan->comp_bpc;
+    if (last_len) *last_len = plan->comp_last;
+    return 0;
+}
 uint64_t crc32c_debug_plan_block(const crc32c_plan *plan) {
     return plan ? uint64_t(reinterpret_cast<uintptr_t>(plan->dp.d)) : 0;
 }

@@ -59,7 +59,6 @@ Gf2Op op_zeros(uint64_t nbytes, uint32_t poly) {
     return acc;
 }
 
-namespace {
 // a * b mod P in the register's reflected representation (bit 31 = x^0).
 uint32_t mulmod(uint32_t a, uint32_t b, uint32_t poly) {
     uint32_t p = 0;
@@ -69,6 +68,19 @@ uint32_t mulmod(uint32_t a, uint32_t b, uint32_t poly) {
     }
     return p;
 }
+
+MulTable::MulTable(uint32_t c, uint32_t poly) {
+    // the 32 basis products, then every entry as the xor of its set bits'
+    for (int k = 0; k < 4; ++k) {
+        t[k][0] = 0;
+        for (int i = 0; i < 8; ++i) {
+            const uint32_t v = mulmod(1u << (8 * k + i), c, poly);
+            for (uint32_t b = 0; b < (1u << i); ++b) t[k][(1u << i) | b] = t[k][b] ^ v;
+        }
+    }
+}
+
+namespace {
 struct PowTable {  // x^(2^k) mod P, k = 0..63
     uint32_t t[64];
     explicit PowTable(uint32_t poly) {

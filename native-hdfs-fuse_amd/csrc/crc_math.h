@@ -38,6 +38,20 @@ Gf2Op op_zeros(uint64_t nbytes, uint32_t poly = kPoly);      // append nbytes ze
 // 32x32 operator compositions: what plan building uses per zero-fill chunk.
 uint32_t shift_zeros(uint32_t reg, uint64_t nbytes, uint32_t poly = kPoly);
 
+// ---- composite CRCs (hdfs_crc32c.h section 6c) ----
+// a * b mod P in the register's reflected representation (bit 31 = x^0): 32
+// shift/xor steps.  mulmod(0, .) == 0, and 1u << 31 is the unit.
+uint32_t mulmod(uint32_t a, uint32_t b, uint32_t poly = kPoly);
+// x^(8 nbytes) mod P: crc(A || B) == mulmod(crc(A), xpow8(|B|)) ^ crc(B) for
+// conditioned CRCs (init ~0, final ~0), with crc(empty) == 0.
+inline uint32_t xpow8(uint64_t nbytes, uint32_t poly = kPoly) { return shift_zeros(1u << 31, nbytes, poly); }
+// Multiplication by one constant c as 4 lookups: t[k][b] = (b << 8 k) * c.
+struct MulTable {
+    uint32_t t[4][256];
+    MulTable(uint32_t c, uint32_t poly);
+    uint32_t mul(uint32_t a) const { return t[0][a & 0xffu] ^ t[1][(a >> 8) & 0xffu] ^ t[2][(a >> 16) & 0xffu] ^ t[3][a >> 24]; }
+};
+
 // Linear part of the CRC over bytes with register starting at 0 (no
 // conditioning): crc(0, M) == lin(M) ^ crc(0, zeros(len)).
 uint32_t lin_bytes(const uint8_t *p, size_t n, uint32_t reg = 0, uint32_t poly = kPoly);

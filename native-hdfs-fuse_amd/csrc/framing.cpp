@@ -8,8 +8,13 @@
 //    sendmsg of two iovecs (prefix, data).
 //  * crc32c_block_md5: OpBlockChecksumResponseProto.md5 (datatransfer.proto:
 //    262-267), the MD5 of a block's big-endian checksum bytes.
+//  * crc32c_combine, crc32c_block_composite, crc32c_file_composite: chunk
+//    checksums combined into the CRC of the bytes (hdfs_crc32c.h section 6c).
+#include <cerrno>
 #include <cstring>
 
+#include "crc_math.h"
+#include "errors.h"
 #include "hdfs_crc32c.h"
 
 namespace {
@@ -189,4 +194,65 @@ extern "C" void crc32c_file_md5(const uint8_t *block_md5s, size_t nblocks, uint8
     Md5 m;
     if (nblocks) m.update(block_md5s, 16 * nblocks);
     m.finish(md5);
+}
+
+// ---- composite CRCs (hdfs_crc32c.h section 6c): the host algebra ----
+//
+// crc(A || B) = crc(A) * x^(8 |B|) ^ crc(B) in GF(2)[x] mod P (crc_math.h
+// mulmod / xpow8).  A block's chunk checksums c_0 .. c_{n-1}, whose chunks
+// after the first are bpc bytes long but for the last (last_len), therefore
+// combine to ((c_0 X + c_1) X + ... + c_{n-2}) x^(8 last_len) ^ c_{n-1} with
+// X = x^(8 bpc): Horner's rule with one constant.
+namespace {
+
+inline uint32_t poly_of(uint32_t flags) { return (flags & CRC32C_TYPE_CRC32) ? hdfs_crc::kPolyIeee : hdfs_crc::kPoly; }
+inline uint32_t stored(uint32_t v, uint32_t flags) { return (flags & CRC32C_BIG_ENDIAN) ? __builtin_bswap32(v) : v; }
+
+// Horner steps below which the 32-step product per step is cheaper than
+// building the 4 x 256 table of X first (32 products and 1024 xors).
+constexpr size_t kTableFrom = 96;
+
+}  // namespace
+
+extern "C" uint32_t crc32c_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t flags) {
+    return hdfs_crc::shift_zeros(crc_a, len_b, poly_of(flags)) ^ crc_b;
+}
+
+extern "C" int crc32c_block_composite(const uint32_t *sums, size_t n, uint32_t bpc, uint32_t last_len, uint32_t flags,
+                                      uint32_t *crc) {
+    using hdfs_crc::fail;
+    if (!crc) return fail(-EINVAL, "crc == NULL");
+    if (flags & ~(CRC32C_BIG_ENDIAN | CRC32C_TYPE_CRC32))
+        return fail(-EINVAL, "a block composite takes only CRC32C_BIG_ENDIAN and CRC32C_TYPE_CRC32 (flags 0x%x)", flags);
+    if (bpc == 0) return fail(-EINVAL, "bpc == 0");
+    if (n == 0) {
+        *crc = 0;
+        return 0;
+    }
+    if (!sums) return fail(-EINVAL, "sums == NULL");
+    if (last_len == 0 || last_len > bpc) return fail(-EINVAL, "last_len %u is not in 1 .. bpc (%u)", last_len, bpc);
+    const uint32_t poly = poly_of(flags);
+    const uint32_t x = hdfs_crc::xpow8(bpc, poly);
+    uint32_t h = 0;
+    if (n - 1 >= kTableFrom) {
+        const hdfs_crc::MulTable t(x, poly);
+        for (size_t i = 0; i + 1 < n; ++i) h = t.mul(h) ^ stored(sums[i], flags);
+    } else {
+        for (size_t i = 0; i + 1 < n; ++i) h = hdfs_crc::mulmod(h, x, poly) ^ stored(sums[i], flags);
+    }
+    *crc = hdfs_crc::shift_zeros(h, last_len, poly) ^ stored(sums[n - 1], flags);
+    return 0;
+}
+
+extern "C" int crc32c_file_composite(const uint32_t *block_crcs, const uint64_t *block_lens, size_t nblocks,
+                                     uint32_t flags, uint32_t *crc) {
+    using hdfs_crc::fail;
+    if (!crc) return fail(-EINVAL, "crc == NULL");
+    if (flags & ~CRC32C_TYPE_CRC32) return fail(-EINVAL, "a file composite takes only CRC32C_TYPE_CRC32 (flags 0x%x)", flags);
+    if (nblocks && (!block_crcs || !block_lens)) return fail(-EINVAL, "block_crcs/block_lens == NULL");
+    const uint32_t poly = poly_of(flags);
+    uint32_t h = 0;
+    for (size_t i = 0; i < nblocks; ++i) h = hdfs_crc::shift_zeros(h, block_lens[i], poly) ^ block_crcs[i];
+    *crc = h;
+    return 0;
 }

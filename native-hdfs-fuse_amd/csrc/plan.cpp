@@ -25,6 +25,69 @@ void HostPlan::clear() {
     pieces.clear();
     consts.clear();
     nchecksums = payload_bytes = 0;
+    comp_bpc = comp_last = 0;
+}
+
+void CompositeShape::add(uint64_t count, uint32_t len, uint32_t chunk_bpc) {
+    if (!count || !ok) return;
+    if (!bpc) bpc = chunk_bpc;
+    if (chunk_bpc != bpc || len > bpc || len == 0 || short_last) {
+        ok = false;  // another bpc, or a chunk after a short one that was not the first
+        return;
+    }
+    if (n == 0) {  // the first chunk's length never enters
+        n = 1;
+        last = len;
+        if (--count == 0) return;
+    }
+    if (len < bpc) {
+        if (count > 1) {
+            ok = false;
+            return;
+        }
+        short_last = true;
+    }
+    n += count;
+    last = len;
+}
+
+void CompositeShape::store(HostPlan *plan) const {
+    const bool is = ok && n > 0;
+    plan->comp_bpc = is ? bpc : 0;
+    plan->comp_last = is ? last : 0;
+}
+
+void packets_composite_shape(const crc32c_packet *pkts, size_t npkts, HostPlan *plan) {
+    // Packets in checksum order: as given when their out_idx already rise
+    // (every batch the library's own packetisers make), else sorted.
+    std::vector<uint32_t> order;
+    bool sorted = true;
+    uint64_t prev = 0;
+    for (size_t i = 0; i < npkts && sorted; ++i) {
+        if (!pkts[i].len) continue;
+        sorted = pkts[i].out_idx >= prev;
+        prev = pkts[i].out_idx;
+    }
+    if (!sorted) {
+        if (npkts > UINT32_MAX) return;
+        for (size_t i = 0; i < npkts; ++i)
+            if (pkts[i].len) order.push_back(uint32_t(i));
+        std::sort(order.begin(), order.end(),
+                  [&](uint32_t a, uint32_t b) { return pkts[a].out_idx < pkts[b].out_idx; });
+    }
+    CompositeShape sh;
+    const size_t count = sorted ? npkts : order.size();
+    for (size_t i = 0; i < count && sh.ok; ++i) {
+        const crc32c_packet &p = pkts[sorted ? i : order[i]];
+        if (!p.len) continue;
+        if (!p.bpc || p.out_idx != sh.n) {  // a gap or an overlap
+            sh.ok = false;
+            break;
+        }
+        sh.add(p.len / p.bpc, p.bpc, p.bpc);
+        sh.add(p.len % p.bpc ? 1 : 0, p.len % p.bpc, p.bpc);
+    }
+    sh.store(plan);
 }
 
 uint64_t HostPlan::items() const {
@@ -247,6 +310,7 @@ int build_plan(const crc32c_packet *pkts, size_t npkts, HostPlan *plan, bool abs
         const int rc = append_packet(pkts[i], plan, absolute);
         if (rc) return rc;
     }
+    packets_composite_shape(pkts, npkts, plan);
     return 0;
 }
 
@@ -301,6 +365,7 @@ int build_write_plan(const crc32c_buffer *buffers, uint32_t n_buffers, uint64_t 
     if (bufferoffset > start[n_buffers] || len > start[n_buffers] - bufferoffset) return -EINVAL;
 
     ZeroCrc zero{poly};
+    CompositeShape shape;
     uint64_t out = 0, sent = 0;
     uint32_t bi = 0;  // buffer holding the current chunk's first byte
     crc32c_packet run{};  // consecutive chunks of one packet inside one data buffer
@@ -385,9 +450,12 @@ int build_write_plan(const crc32c_buffer *buffers, uint32_t n_buffers, uint64_t 
                 plan->seg.push_back(s);
         }
         if (int rc = flush()) return rc;
+        shape.add(nfullp, bpc, bpc);
+        shape.add(plen % bpc ? 1 : 0, uint32_t(plen % bpc), bpc);
         out += nch;
         sent += plen;
     }
+    shape.store(plan);
     // append_packet counted the runs; the totals cover every chunk.
     plan->nchecksums = out;
     plan->payload_bytes = len;
@@ -426,6 +494,17 @@ extern "C" int crc32c_debug_plan_abs(const crc32c_packet *pkts, size_t npkts, in
     if (gen && gen_cap)
         std::memcpy(gen, plan.gen.data(),
                     sizeof(hdfs_crc::GenItem) * (plan.gen.size() < gen_cap ? plan.gen.size() : gen_cap));
+    return 0;
+}
+
+extern "C" int crc32c_debug_packets_composite_shape(const crc32c_packet *pkts, size_t npkts, uint32_t *bpc,
+                                                    uint32_t *last_len) {
+    hdfs_crc::HostPlan plan;
+    if (npkts && !pkts) return -EINVAL;
+    hdfs_crc::packets_composite_shape(pkts, npkts, &plan);
+    if (!plan.comp_bpc) return -EINVAL;
+    if (bpc) *bpc = plan.comp_bpc;
+    if (last_len) *last_len = plan.comp_last;
     return 0;
 }
 

@@ -120,6 +120,11 @@ struct HostPlan {
     std::vector<ConstRun> consts;
     uint64_t nchecksums = 0;     // max(out_idx + nchunks)
     uint64_t payload_bytes = 0;  // sum of packet lengths (zero-fill bytes included)
+    // Composite shape (hdfs_crc32c.h section 6c): the chunks, in checksum
+    // order from index 0 without gaps, are [<= bpc], bpc, ..., bpc, [last_len]
+    // under one bpc -- then the checksum array combines into the CRC of the
+    // bytes with two constants.  comp_bpc == 0: not of that form.
+    uint32_t comp_bpc = 0, comp_last = 0;
     void clear();
     uint64_t items() const;      // work items of a launch (tiles, gen / seg pairs, const runs)
 };
@@ -130,6 +135,21 @@ struct HostPlan {
 // start up to 15 bytes before a chunk (same 4 KiB page required then, else a
 // payload offset >= 16).
 int build_plan(const crc32c_packet *pkts, size_t npkts, HostPlan *plan, bool absolute = false);
+
+// Follows a plan's chunks in checksum order as runs of `count` chunks of `len`
+// bytes under `bpc`, and tells whether they have the composite shape.
+struct CompositeShape {
+    uint64_t n = 0;      // chunks so far
+    uint32_t bpc = 0;    // the one bpc (0: none seen yet)
+    uint32_t last = 0;   // length of the latest chunk
+    bool short_last = false;  // a chunk after the first was shorter than bpc: nothing may follow it
+    bool ok = true;
+    void add(uint64_t count, uint32_t len, uint32_t chunk_bpc);
+    void store(HostPlan *plan) const;  // comp_bpc / comp_last (0 / 0 when not of the form or empty)
+};
+// The composite shape of a packet batch (zero-length packets ignored; packets
+// in any order, their out_idx must tile 0 .. n without gaps or overlaps).
+void packets_composite_shape(const crc32c_packet *pkts, size_t npkts, HostPlan *plan);
 
 // Appends one packet's work items (no reset; updates the totals).
 int append_packet(const crc32c_packet &p, HostPlan *plan, bool absolute = false);

@@ -200,6 +200,9 @@ struct crc32c_plan {
     hdfs_crc::DevicePlan dp;
     uint64_t nchecksums = 0, payload_bytes = 0;
     uint32_t flags = 0;
+    // The composite shape of the plan's chunks (plan.h HostPlan::comp_bpc;
+    // 0: the checksums do not combine with two constants).
+    uint32_t comp_bpc = 0, comp_last = 0;
     // Absolute plans (CRC32C_DEVICE_ADDRESSES, crc32c_plan_create_buffers):
     // offsets are relative to this device address (the lowest address read,
     // rounded down to 16), which the launches pass as the payload base.
@@ -227,6 +230,8 @@ int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *co
                 hipStream_t stream, hipEvent_t stop);
 // Loads the block-MD5 kernels' code object onto the current device (crc32c_md5.hip).
 hipError_t preload_md5_kernels();
+// The same for the composite-CRC kernels (crc32c_composite.hip).
+hipError_t preload_composite_kernels();
 // A destroyed plan's blocks back to the pools once its launches are done.
 void release_plan_blocks(crc32c_plan *plan);
 // Context teardown: waits for the releases, frees every pooled block.
