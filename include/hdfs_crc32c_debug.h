@@ -52,6 +52,11 @@ size_t crc32c_debug_lds_image(void *dst, size_t cap, uint32_t *c_lg5, uint32_t *
  * finishing operators N_q, the Z^(512 s) shifts); returns its size and
  * fills dst when cap is large enough. */
 size_t crc32c_debug_lds_image_s4(void *dst, size_t cap, uint32_t flags);
+/* The split form of that image, which the large-batch builds and the
+ * resident kernel stage: 16 columns of each byte table, T_m[b] at b * 256 +
+ * m * 64 + 4 c (c = 0..15), then the N_q and Z^(512 s) sections unchanged
+ * (at 65536 and 81920). */
+size_t crc32c_debug_lds_image_s4_split(void *dst, size_t cap, uint32_t flags);
 /* The affine constants of the checksum type in `flags` (CRC32C_TYPE_CRC32 or not). */
 void crc32c_debug_affine_constants(uint32_t flags, uint32_t *c_lg5, uint32_t *c_small4);
 

@@ -237,6 +237,7 @@ def _bind(L):
         "crc32c_debug_plan_abs": (i32, [vp, sz, i32, vp, sz, vp, sz, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "crc32c_debug_lds_image": (sz, [vp, sz, vp, vp]),
         "crc32c_debug_lds_image_s4": (sz, [vp, sz, u32]),
+        "crc32c_debug_lds_image_s4_split": (sz, [vp, sz, u32]),
         "crc32c_plan_verify": (i32, [vp, vp, vp, vp, vp]),
         "crc32c_plan_verify_bitmap": (i32, [vp, vp, vp, vp, vp, vp]),
         "crc32c_frame_packets": (sz, [vp, sz, vp, u32, u64, ctypes.c_int64, u32, vp, sz, vp]),
@@ -1042,6 +1043,14 @@ def debug_lds_image_s4(flags: int = 0):
     n = int(lib().crc32c_debug_lds_image_s4(None, 0, flags))
     img = np.zeros(n, np.uint8)
     lib().crc32c_debug_lds_image_s4(_np_ptr(img), n, flags)
+    return img
+
+
+def debug_lds_image_s4_split(flags: int = 0):
+    """The split S4 image the large-batch builds stage (16 columns per byte table)."""
+    n = int(lib().crc32c_debug_lds_image_s4_split(None, 0, flags))
+    img = np.zeros(n, np.uint8)
+    lib().crc32c_debug_lds_image_s4_split(_np_ptr(img), n, flags)
     return img
 
 

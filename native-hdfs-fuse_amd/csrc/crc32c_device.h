@@ -20,11 +20,13 @@
 //    non-temporal buffer loads bounded by the tile (partial tiles read zeros).
 //  * Lookups, production (kModeS4): each lane chains its 16-byte piece
 //    d0..d3 through the slicing-by-4 step S (crc32c.c's crc32c_table[0..3],
-//    one 4-byte column per lane so the 32 lanes of a half-wave always hit 32
-//    different banks): u = S(S(S(d0) ^ d1) ^ d2) ^ d3, then one column-
-//    specific operator N_q = Z_{16(31-q)} o S (8 nibble lookups) moves the
-//    piece's contribution to the block end.  20 LDS lookups + 37 VALU per
-//    16 bytes; 152 KiB of LDS, one workgroup per CU, 12 waves (768 threads).
+//    16 four-byte columns per table: in one lookup instruction lanes 0-15 of
+//    a half-wave read one table of a pair and lanes 16-31 the other, so its
+//    32 lanes always hit 32 different banks): u = S(S(S(d0) ^ d1) ^ d2) ^ d3,
+//    then one column-specific operator N_q = Z_{16(31-q)} o S (8 nibble
+//    lookups) moves the piece's contribution to the block end.  20 LDS
+//    lookups + 37 VALU per 16 bytes; 88 KiB of LDS, one workgroup per CU,
+//    12 waves (768 threads).
 //  * Wave-level reduction: each lane's per-piece value is XOR-reduced over
 //    the 32 lanes of its block with a DPP reduce-scatter, which also packs
 //    the 16 block results of a tile into 16 lanes for one coalesced store.
@@ -169,26 +171,60 @@ __device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t mask, uint32_t c
 // Per-lane LDS address constants: the lane's column offset, and the same
 // with the base of the S4 image's upper byte-table pair / N_q section.
 struct LaneCols {
-    uint32_t col4;  // (lane & 31) * 4
-    uint32_t hi;    // col4 | 65536
-    uint32_t nib;   // col4 | kS4NibOff
+    uint32_t col4;  // (lane & 31) * 4; split image: col4 | (col4 ^ 64) << 8
+    uint32_t hi;    // col4 | 65536; split image: unused
+    uint32_t nib;   // col4 | the image's N_q offset
     uint32_t toff;  // T1 - T0 (= T3 - T2) in bytes: 128, or 1024 in the compact image
+    uint32_t sel[4];  // split image: the v_perm selectors of a step's four lookups
 };
 
-// S4 image layouts (template parameter IMG): the full image (32 replica
-// columns of T0..T3) and the compact image (T0..T3 once each, for small
-// batches: crc_math.h kS4C*).  (A half-column image -- 16 replica columns,
-// 88 KiB staged -- measured +-0 and was removed)
-constexpr int kImgFull = 0, kImgCompact = 2;
+// S4 image layouts (template parameter IMG): the split image (16 replica
+// columns of T0..T3, the two lane halves of a half-wave reading different
+// tables: every full-image production build), the 32-column image it is
+// derived from (32 replica columns; A/B in the debug library, kModeImg32) and
+// the compact image (T0..T3 once each, for small batches: crc_math.h kS4C*).
+// (Round 1's half-column image -- 16 replica columns, every lane reading the
+// same table, so 2-way bank conflicts -- lost sustained and was removed,
+// DESIGN.md section 4.)
+// kImgSplitLean: the split image with only the first selector held and the
+// other three derived at each use (builds at their register cap).
+constexpr int kImgFull = 0, kImgSplit = 1, kImgCompact = 2, kImgSplitLean = 3;
+constexpr bool is_split(int img) { return img == kImgSplit || img == kImgSplitLean; }
 constexpr uint32_t kS4CNibOff = uint32_t(hdfs_crc::kS4CNibOff);
 constexpr uint32_t kS4CShiftOff = uint32_t(hdfs_crc::kS4CShiftOff);
 constexpr uint32_t kS4CStageBytes = (uint32_t(hdfs_crc::kS4CBytes) + 1023u) / 1024u * 1024u;
+constexpr uint32_t kS4SNibOff = uint32_t(hdfs_crc::kS4SNibOff);
+constexpr uint32_t kS4SShiftOff = uint32_t(hdfs_crc::kS4SShiftOff);
+constexpr uint32_t kS4SStageBytes = (uint32_t(hdfs_crc::kS4SBytes) + 1023u) / 1024u * 1024u;
+static_assert(kS4SStageBytes <= hdfs_crc::kTableAllocS4S, "staging reads past the device table");
 
+// The staged bytes, the Z offset and the place in the device table of an S4
+// image.
+template <int IMG>
+struct S4Image {
+    static constexpr uint32_t kStage = IMG == kImgCompact ? kS4CStageBytes : is_split(IMG) ? kS4SStageBytes : kS4StageBytes;
+    static constexpr uint32_t kShift = IMG == kImgCompact ? kS4CShiftOff : is_split(IMG) ? kS4SShiftOff : kS4ShiftOff;
+    static constexpr uint32_t kTableOff = IMG == kImgCompact ? hdfs_crc::kS4COff : is_split(IMG) ? hdfs_crc::kS4SOff : 0u;
+};
+
+// Split image, lane column q: the lane's base col4 = 4 q lies in T0's 16
+// columns for q < 16 and in T1's (at +64 in the row) for q >= 16, col4 ^ 64
+// in the other table of the pair; T2 / T3 sit 128 bytes on.  Lookup A reads
+// base col4 with byte 3 of v (q < 16: T0) or byte 2 (q >= 16: T1), lookup B
+// base col4 ^ 64 with the other byte, lookups C / D the same 128 bytes on
+// with bytes 1 / 0.  Both bases travel in one register (bytes 0 and 1); a
+// selector picks the base byte and the byte of v (4-7), 0x0C = zero.
 template <int IMG>
 __device__ __forceinline__ LaneCols lane_cols(uint32_t q) {
     if (IMG == kImgCompact)  // T_m[b] at m * 1024 + 4 b: col4 = T0 base, hi = T2 base
-        return LaneCols{0u, 2048u, (q << 2) | kS4CNibOff, 1024u};
-    return LaneCols{q << 2, (q << 2) | 65536u, (q << 2) | kS4NibOff, 128u};
+        return LaneCols{0u, 2048u, (q << 2) | kS4CNibOff, 1024u, {0u, 0u, 0u, 0u}};
+    if (is_split(IMG)) {
+        const uint32_t col4 = q << 2;
+        const uint32_t a = q < 16u ? 0x0C0C0700u : 0x0C0C0600u;
+        return LaneCols{col4 | (col4 ^ 64u) << 8, 0u, col4 | kS4SNibOff, 64u,
+                        {a, a ^ 0x0101u, a ^ 0x0200u, a ^ 0x0301u}};
+    }
+    return LaneCols{q << 2, (q << 2) | 65536u, (q << 2) | kS4NibOff, 128u, {0u, 0u, 0u, 0u}};
 }
 
 // Byte j of v into address bits 8..15 and the column base's bytes 0 and 2
@@ -199,9 +235,20 @@ __device__ __forceinline__ uint32_t byte_addr(uint32_t v, uint32_t base) {
     return __builtin_amdgcn_perm(v, base, 0x0C020000u | uint32_t(4 + J) << 8);
 }
 
+// sel ^ K, computed where `at` becomes available (the unused operand keeps
+// the compiler from hoisting the XOR out of the tile loop and holding its
+// result in a register instead).
+template <uint32_t K>
+__device__ __forceinline__ uint32_t sel_xor(uint32_t sel, uint32_t at) {
+    uint32_t r;
+    asm("v_xor_b32 %0, %1, %2 ; %3" : "=v"(r) : "n"(K), "v"(sel), "v"(at));
+    return r;
+}
+
 // One slicing-by-4 step: S(v) ^ next, S(v) = T3[v.b0] ^ T2[v.b1] ^ T1[v.b2]
-// ^ T0[v.b3] (each table replicated over the lane columns of the image, so
-// the 32 lanes of a half-wave always hit 32 different banks).
+// ^ T0[v.b3] (each table replicated over lane columns of the image so that
+// the 32 lanes of a half-wave always hit 32 different banks: 32 columns, or
+// 16 in the split image, where the lane halves read different tables).
 template <int IMG>
 __device__ __forceinline__ uint32_t s4(const uint8_t *lds, const LaneCols &c, uint32_t v, uint32_t next) {
     if (IMG == kImgCompact) {  // byte j of v -> bits 2..9 (v_bfe + v_lshl_add), one copy of each table
@@ -210,6 +257,17 @@ __device__ __forceinline__ uint32_t s4(const uint8_t *lds, const LaneCols &c, ui
         const uint32_t a1 = lds_u32(lds, (__builtin_amdgcn_ubfe(v, 16, 8) << 2) + c.toff);
         const uint32_t a0 = lds_u32(lds, (v >> 24) << 2);
         return xor3(xor3(a3, a2, a1), a0, next);
+    }
+    if (is_split(IMG)) {  // (which table a lookup reads depends on the lane half: lane_cols)
+        const bool lean = IMG == kImgSplitLean;
+        const uint32_t s1 = lean ? sel_xor<0x0101u>(c.sel[0], v) : c.sel[1];
+        const uint32_t s2 = lean ? sel_xor<0x0200u>(c.sel[0], v) : c.sel[2];
+        const uint32_t s3 = lean ? sel_xor<0x0301u>(c.sel[0], v) : c.sel[3];
+        const uint32_t a = lds_u32(lds, __builtin_amdgcn_perm(v, c.col4, c.sel[0]));
+        const uint32_t b = lds_u32(lds, __builtin_amdgcn_perm(v, c.col4, s1));
+        const uint32_t cc = lds_u32(lds, __builtin_amdgcn_perm(v, c.col4, s2) + 128u);
+        const uint32_t d = lds_u32(lds, __builtin_amdgcn_perm(v, c.col4, s3) + 128u);
+        return xor3(xor3(cc, d, a), b, next);
     }
     const uint32_t a3 = lds_u32(lds, byte_addr<0>(v, c.hi) + c.toff);    // T3: upper pair, odd
     const uint32_t a2 = lds_u32(lds, byte_addr<1>(v, c.hi));             // T2: upper pair, even
@@ -241,7 +299,7 @@ __device__ __forceinline__ uint32_t piece(const uint8_t *lds, uint4 d, const Lan
 // Z^(512*s)(x), s in 1..15, from 8 nibble tables (16 entries each).
 template <bool S4, int IMG>
 __device__ __forceinline__ uint32_t zshift(const uint8_t *lds, uint32_t s, uint32_t x) {
-    const uint32_t base = (!S4 ? kShiftOff : IMG == kImgCompact ? kS4CShiftOff : kS4ShiftOff) + (s - 1u) * 512u;
+    const uint32_t base = (!S4 ? kShiftOff : S4Image<IMG>::kShift) + (s - 1u) * 512u;
     uint32_t r = 0;
 #pragma unroll
     for (int t = 0; t < 8; ++t) r ^= lds_u32(lds, base + t * 64u + ((x >> (4 * t)) & 15u) * 4u);
@@ -1048,7 +1106,6 @@ __global__ __launch_bounds__(THREADS, WPS) void hdfs_crc32c_plan_kernel(hdfs_crc
     constexpr bool NOSTAGE = (MODE & kModeNoStage) != 0;
     constexpr bool VERIFY = (MODE & kModeVerify) != 0;
     constexpr bool C = S4 && (MODE & kModeS4C) != 0;
-    constexpr int IMG = C ? kImgCompact : kImgFull;
     constexpr bool GENERAL = (MODE & kModeGeneral) != 0;
     constexpr int GEN = !GENERAL ? 0
                                  : ((MODE & kModeNoGItems) ? 0 : kGenItems) |
@@ -1056,6 +1113,13 @@ __global__ __launch_bounds__(THREADS, WPS) void hdfs_crc32c_plan_kernel(hdfs_crc
                                                               : (kGenShift | kGenGroup2)) |
                                        ((MODE & kModeGHoist) ? kGenHoist : 0) | ((MODE & kModeHalfT) ? kGenHalf : 0) |
                                        ((!(MODE & (kModeNoGItems | kModeNoPadT))) ? kGenPadded : 0);
+    // The split image; the 32-column image is an A/B in the debug library
+    // only, and the nibble variant has no S4 image.  The builds with the
+    // general-tile code and the shifted loads or half tiles sit at the
+    // register cap of 3 waves per SIMD: holding the split image's four
+    // selectors made them spill, so they derive three of them at each use.
+    constexpr bool LEAN = (GEN & kGenItems) && (GEN & (kGenShift | kGenHalf));
+    constexpr int IMG = C ? kImgCompact : (!S4 || (MODE & kModeImg32)) ? kImgFull : LEAN ? kImgSplitLean : kImgSplit;
     constexpr bool EARLY = (MODE & kModeEarly) != 0;
     constexpr bool OVL = !EARLY && (MODE & kModeOvl) != 0;
     constexpr bool QUARTER = (MODE & kModeQuarter) != 0;
@@ -1063,14 +1127,14 @@ __global__ __launch_bounds__(THREADS, WPS) void hdfs_crc32c_plan_kernel(hdfs_crc
     constexpr int SPLIT = (MODE & kModeHalves) ? 2 : 4;  // units per tile
     constexpr int AUX = NT ? 2 : 0;
     constexpr uint32_t kWaves = THREADS / 64;
-    constexpr uint32_t kStage = !S4 ? kStageBytes : C ? kS4CStageBytes : kS4StageBytes;
+    constexpr uint32_t kStage = !S4 ? kStageBytes : S4Image<IMG>::kStage;
     // One LDS array: the tables, then the workgroup's tile counter and (VERIFY)
     // its mismatch count, first bad index and bad-index list (vacc).
     __shared__ __attribute__((aligned(16))) uint8_t lds[kStage + 32 + (VERIFY ? 4 * kBadList : 0)];
     uint32_t *pool_ctr = reinterpret_cast<uint32_t *>(lds + kStage);
     uint32_t *vacc = pool_ctr + 1;
     uint32_t *exit_ctr = pool_ctr + 5;  // waves of the workgroup done
-    const uint8_t *table = !S4 ? p.table : C ? p.table_s4 + hdfs_crc::kS4COff : p.table_s4;
+    const uint8_t *table = !S4 ? p.table : p.table_s4 + S4Image<IMG>::kTableOff;
     const int lane = int(threadIdx.x & 63u);
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave in workgroup
 
@@ -1115,7 +1179,7 @@ __global__ __launch_bounds__(THREADS, WPS) void hdfs_crc32c_plan_kernel(hdfs_crc
     };
     // EARLY: the first tile's loads go out before the staging (their latency
     // overlaps it).  Measured slower for large batches -- 3072 waves x 8 KiB
-    // in flight queue the 152 KiB staging DMA behind them -- so only the
+    // in flight queue the staging DMA behind them -- so only the
     // small-batch kernel (compact image, 28 KiB) does it.
     if (EARLY && t < tend) load_next(t);
     // Stage the tables by LDS-DMA (1 KiB per wave instruction, no VGPRs); a
@@ -1123,11 +1187,9 @@ __global__ __launch_bounds__(THREADS, WPS) void hdfs_crc32c_plan_kernel(hdfs_crc
     const bool tables = (p.ntiles | p.ngen | p.nseg) != 0;
     constexpr uint32_t kStageChunks = kStage / 1024u;
     // (a batch with no Z^(512 s) shift -- bpc-512 tiles only -- leaves the
-    // image's Z section out: 144 of 152 chunks, compact 20 of 28)
-    constexpr uint32_t kNoZChunks = !S4 ? kStageChunks : C ? uint32_t(hdfs_crc::kS4CShiftOff / 1024u)
-                                                           : uint32_t(hdfs_crc::kS4ShiftOff / 1024u);
-    static_assert(!S4 || kNoZChunks * 1024u == (C ? hdfs_crc::kS4CShiftOff : hdfs_crc::kS4ShiftOff),
-                  "the Z section starts on a staging chunk");
+    // image's Z section out: split 80 of 88 chunks, compact 20 of 28, 32-column 144 of 152)
+    constexpr uint32_t kNoZChunks = !S4 ? kStageChunks : S4Image<IMG>::kShift / 1024u;
+    static_assert(!S4 || kNoZChunks * 1024u == S4Image<IMG>::kShift, "the Z section starts on a staging chunk");
     const uint32_t nstage = p.skip_z ? kNoZChunks : kStageChunks;
     if (!NOSTAGE && tables) {
         // Every workgroup copies the same chunks: start each one at a

@@ -5,14 +5,15 @@
 // loads, 12 waves (768 threads) per workgroup and one workgroup per CU, in
 // these builds, each storing checksums (crc32c_plan_exec) or comparing them
 // (crc32c_plan_verify):
-//   * full image, power-of-two tiles only: the bulk path (config 2);
+//   * full image (its split form: 16 columns per byte table, 88 KiB staged),
+//     power-of-two tiles only: the bulk path (config 2);
 //   * full image with the general-tile code (bpc outside 512 * 2^k, packet
 //     tails) and the shifted loads of tiles off 16-byte alignment, in three
 //     forms: both paths, general tiles only, shifted tiles only (a build
 //     without the path a batch does not need has its registers and schedule
 //     to the other path); the both-paths form, which padded chunks run,
 //     computes a general item's next subtile facts ahead (kModeGHoist);
-//   * compact image (28 KiB staged instead of 152 KiB, with the general-tile
+//   * compact image (28 KiB staged instead of 88 KiB, with the general-tile
 //     code): batches of at most kSmallBatchItemsPerCu work items per CU,
 //     where the table staging is most of a launch (one 4 MiB block: 5.8 ->
 //     5.2 us);

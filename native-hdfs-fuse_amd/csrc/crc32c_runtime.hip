@@ -100,7 +100,7 @@ static bool has_general(const HostPlan &hp) {
 // Some work item shifts block results by Z^(512 s): power-of-two tiles of
 // bpc > 512 (lg > 0), general tiles and the general / spanning items.  A
 // batch of bpc-512 tiles only (configs 2, 3, 4) stages the image without
-// its Z section: 144 of 152 KiB (full image), 20 of 28 KiB (compact).
+// its Z section: 80 of 88 KiB (split image), 20 of 28 KiB (compact).
 static bool needs_z(const HostPlan &hp) {
     if (!hp.gen.empty() || !hp.seg.empty()) return true;
     for (const FastTile &t : hp.tiles)
@@ -980,6 +980,7 @@ int crc32c_ctx_create(int device, crc32c_ctx **out) {
         build_lds_image_s4(img4.data(), poly);
         compact_s4_image(img4.data(), img4.data() + kS4COff);  // small batches
         zero_crc_table(reinterpret_cast<uint32_t *>(img4.data() + kZeroCrcOff), poly);  // general items
+        split_s4_image(img4.data(), img4.data() + kS4SOff);  // large batches, the resident kernel
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_table_s4[ty]), kTableAllocS4Full));
         HIP_TRY(hipMemcpy(c->d_table_s4[ty], img4.data(), kTableAllocS4Full, hipMemcpyHostToDevice));
     }

@@ -181,6 +181,13 @@ void compact_s4_image(const uint8_t *full, uint8_t *dst) {
     std::memcpy(dst + kS4CNibOff, full + kS4NibOff, kS4Bytes - kS4NibOff);
 }
 
+void split_s4_image(const uint8_t *full, uint8_t *dst) {
+    for (uint32_t b = 0; b < 256; ++b)
+        for (uint32_t m = 0; m < 4; ++m)  // columns 0..15 of T_m
+            std::memcpy(dst + b * 256u + m * 64u, full + (m >> 1) * 65536u + b * 256u + (m & 1u) * 128u, 64);
+    std::memcpy(dst + kS4SNibOff, full + kS4NibOff, kS4Bytes - kS4NibOff);
+}
+
 void affine_constants(uint32_t c_lg[5], uint32_t c_small[4], uint32_t poly) {
     // crc(0, zeros(n)) = Z^n(0xffffffff) ^ 0xffffffff (crc32c.c:237, 312).
     for (int lg = 0; lg < 5; ++lg) c_lg[lg] = op_zeros(512ull << lg, poly).apply(0xffffffffu) ^ 0xffffffffu;

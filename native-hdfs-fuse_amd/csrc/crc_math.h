@@ -97,6 +97,19 @@ constexpr size_t kS4CBytes = kS4CShiftOff + kMaxShift * 512;
 // Fills `dst` (kS4CBytes) from a full S4 image.
 void compact_s4_image(const uint8_t *full, uint8_t *dst);
 
+// The split S4 image (large batches): 16 replica columns of each byte table,
+// the four tables side by side in one 256-byte row per byte value: T_m[b] at
+// b * 256 + m * 64 + 4 c, c = 0..15.  Lanes 0-15 of a half-wave read one
+// table of a pair (T0/T1, T2/T3) while lanes 16-31 read the other, so the 32
+// lookups of one instruction still hit 32 different banks (crc32c_device.h
+// s4<kImgSplit>).  Then the N_q section (column-specific: all 32 columns)
+// and the Z^(512 s) section as in the full image.
+constexpr size_t kS4SNibOff = 65536;
+constexpr size_t kS4SShiftOff = kS4SNibOff + (kS4ShiftOff - kS4NibOff);
+constexpr size_t kS4SBytes = kS4SShiftOff + kMaxShift * 512;
+// Fills `dst` (kS4SBytes) from a full S4 image.
+void split_s4_image(const uint8_t *full, uint8_t *dst);
+
 // Fills `dst` (kS4Bytes) with the slicing-by-4 LDS image.
 void build_lds_image_s4(uint8_t *dst, uint32_t poly = kPoly);
 // S(u): the register after feeding the 4 bytes of u (little-endian) into register 0.

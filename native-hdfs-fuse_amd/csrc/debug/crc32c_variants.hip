@@ -108,9 +108,15 @@ constexpr Variant kVariants[] = {
     {95, "s4c_wg512_nt_quarter_nopad_early_prodgrid", 512, 1, true, true},
     // the full-image general build (49) without the table staging: real
     // lookups in whatever the LDS holds -- right only after a launch that left
-    // the full CRC32C image there, so not exact; the control of the cold-LDS
+    // the same image there, so not exact; the control of the cold-LDS
     // tests (lds_poison.hip: after a poison it must be wrong)
     {96, "s4_nt_nostage_prodgrid", 768, 1, false, true},
+    // the power-of-two production build (62) on the 32-column S4 image (152
+    // KiB staged, every lane of a lookup in the same table) that production
+    // staged before the split image; stamped twins of it and of 62
+    {97, "s4_nt_pow2only_img32_prodgrid", 768, 1, true, true},
+    {98, "s4_nt_pow2only_img32_stamps_prodgrid", 768, 1, true, true},
+    {99, "s4_nt_pow2only_stamps_prodgrid", 768, 1, true, true},
 };
 
 const Variant *find(int v) {
@@ -138,8 +144,8 @@ hipError_t launch_variant(const hdfs_crc::KParams &p, const Variant &v, uint32_t
     // small-batch builds do: plans with such tiles are refused)
     if (((v.id >= 82 && v.id <= 88) || v.id == 95) && (p.general & (hdfs_crc::kGeneralPadded | hdfs_crc::kGeneralHalf)))
         return hipErrorInvalidValue;
-    // (89-94 carry no general-tile code at all: aligned power-of-two plans only)
-    if (v.id >= 89 && v.id <= 94 && p.general) return hipErrorInvalidValue;
+    // (89-94 and 97-99 carry no general-tile code at all: aligned power-of-two plans only)
+    if (((v.id >= 89 && v.id <= 94) || (v.id >= 97 && v.id <= 99)) && p.general) return hipErrorInvalidValue;
     switch (v.id) {
     case 1: HDFS_LAUNCH(1024, 8, kModeNt | kModeGeneral); break;
     case 2: HDFS_LAUNCH(1024, 4, kS4Nt); break;
@@ -195,6 +201,9 @@ hipError_t launch_variant(const hdfs_crc::KParams &p, const Variant &v, uint32_t
     case 94: HDFS_LAUNCH(512, 2, kModeS4 | kModeNt | kModeS4C); break;
     case 95: HDFS_LAUNCH(512, 2, kS4Nt | kModeS4C | kModeNoPadT | kModeQuarter | kModeEarly); break;
     case 96: HDFS_LAUNCH(768, 3, kS4Nt | kModeNoStage); break;
+    case 97: HDFS_LAUNCH(768, 3, kModeS4 | kModeNt | kModeImg32); break;
+    case 98: HDFS_LAUNCH(768, 3, kModeS4 | kModeNt | kModeImg32 | kModeStamps); break;
+    case 99: HDFS_LAUNCH(768, 3, kModeS4 | kModeNt | kModeStamps); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -22,7 +22,11 @@ constexpr uint32_t kTableAllocS4C = ((uint32_t(kS4CBytes) + 16384 - 1) / 16384) 
 // After it (at kZeroCrcOff): crc(0, zeros(n)) for n = 0 .. kZeroCrcMax
 // (crc_math.h zero_crc_table), read by general items with scalar loads.
 constexpr uint32_t kZeroCrcOff = kS4COff + kTableAllocS4C;
-constexpr uint32_t kTableAllocS4Full = kZeroCrcOff + ((4 * (kZeroCrcMax + 1) + 16384 - 1) / 16384) * 16384;
+// After it (at kS4SOff): the split S4 image (crc_math.h kS4S*), which the
+// large-batch builds and the resident kernel stage.
+constexpr uint32_t kS4SOff = kZeroCrcOff + ((4 * (kZeroCrcMax + 1) + 16384 - 1) / 16384) * 16384;
+constexpr uint32_t kTableAllocS4S = ((uint32_t(kS4SBytes) + 16384 - 1) / 16384) * 16384;
+constexpr uint32_t kTableAllocS4Full = kS4SOff + kTableAllocS4S;
 
 // One block of a multi-block launch (crc32c_plan_exec_blocks): the plan's
 // work items describe one block's shape; block b's copy of item i reads at
@@ -44,7 +48,7 @@ struct KParams {
     const uint8_t *payload;
     uint32_t *out;
     const uint8_t *table;     // kLdsBytes: the nibble image (A/B variant 1)
-    const uint8_t *table_s4;  // kS4Bytes: the slicing-by-4 image (production)
+    const uint8_t *table_s4;  // the slicing-by-4 images (full, compact, zero-CRC table, split: kTableAllocS4Full)
     uint32_t ntiles;
     uint32_t ngen;
     uint32_t nseg;

@@ -538,6 +538,16 @@ extern "C" size_t crc32c_debug_lds_image_s4(void *dst, size_t cap, uint32_t flag
     return hdfs_crc::kS4Bytes;
 }
 
+extern "C" size_t crc32c_debug_lds_image_s4_split(void *dst, size_t cap, uint32_t flags) {
+    const uint32_t poly = (flags & CRC32C_TYPE_CRC32) ? hdfs_crc::kPolyIeee : hdfs_crc::kPoly;
+    if (dst && cap >= hdfs_crc::kS4SBytes) {
+        std::vector<uint8_t> full(hdfs_crc::kS4Bytes);
+        hdfs_crc::build_lds_image_s4(full.data(), poly);
+        hdfs_crc::split_s4_image(full.data(), static_cast<uint8_t *>(dst));
+    }
+    return hdfs_crc::kS4SBytes;
+}
+
 extern "C" void crc32c_debug_affine_constants(uint32_t flags, uint32_t *c_lg, uint32_t *c_small) {
     const uint32_t poly = (flags & CRC32C_TYPE_CRC32) ? hdfs_crc::kPolyIeee : hdfs_crc::kPoly;
     hdfs_crc::affine_constants(c_lg, c_small, poly);

@@ -43,6 +43,8 @@ constexpr int kModeNoPadT = 2097152;  // (general builds) no padded power-of-two
                                       // builds (their code there cost config 3 ~4 %, round 5)
 constexpr int kModeOvl = 524288;      // A/B: the first tile's loads issued right after the table staging's, before
                                       // the barrier that waits for the staging (their latencies overlap)
+constexpr int kModeImg32 = 4194304;   // A/B (debug library only): the 32-column S4 image (152 KiB staged) instead
+                                      // of the split image (88 KiB) every full-image production build stages
 
 }  // namespace hdfs_crc_dev
 

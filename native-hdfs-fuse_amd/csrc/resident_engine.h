@@ -63,7 +63,7 @@ using hdfs_crc::FastTile;
 
 constexpr uint32_t kRing = 64;       // tickets in flight at most
 // (the kernel is a template on WAVES per workgroup -- one workgroup per CU,
-// 152 KiB of LDS --, PHASES, the blocks processed at once, and PER, the
+// 88 KiB of LDS --, PHASES, the blocks processed at once, and PER, the
 // worker waves per workgroup and phase that take tiles (2: one 8 KiB tile
 // each; 1: both tiles of the workgroup, both loaded before the first one's
 // lookups, so twice the phases fit).  The product instantiates 16 / 7 / 2
@@ -195,7 +195,7 @@ __device__ __forceinline__ void rtile_reduce(const RParams &p, const uint8_t *ld
     if (lg) {
         const uint32_t nbc = 1u << lg;
         const uint32_t s = nbc - 1u - (blk & (nbc - 1u));
-        if (s) x = zshift<true, kImgFull>(lds, s, x);
+        if (s) x = zshift<true, kImgSplit>(lds, s, x);
         x ^= static_cast<uint32_t>(__shfl_xor(static_cast<int>(x), 32));
         if (lg >= 2) x ^= dpp<kDppXor8>(x);
         if (lg >= 3) x ^= dpp<kDppXor2>(x);
@@ -206,7 +206,7 @@ __device__ __forceinline__ void rtile_reduce(const RParams &p, const uint8_t *ld
 __device__ __forceinline__ void rtile_finish(const RParams &p, const uint8_t *lds, uint32_t *out, const FastTile &t,
                                              uint4 v[8], int lane) {
     uint32_t pc[8];
-    tile_pieces<0, true, kImgFull>(lds, v, pc, lane, NoPrep{});
+    tile_pieces<0, true, kImgSplit>(lds, v, pc, lane, NoPrep{});
     rtile_reduce(p, lds, out, t, pc, lane);
 }
 __device__ __forceinline__ void run_tile(const RParams &p, const uint8_t *lds, const uint8_t *payload,
@@ -250,10 +250,10 @@ __device__ __forceinline__ void run_ptile(const RParams &p, const uint8_t *lds, 
     const uint32_t b = r & 3u, li = ((t.meta & 0xffu) - 1u) >> 1;
     const int ll = int(((t.meta & 0xffu) - 1u) & 1u) * 32 + 31;
     switch (r >> 2) {
-        case 0: tile_pieces<0, true, kImgFull>(lds, v, pc, lane, ShiftPrep<0>{v, b, lane, li, ll}); break;
-        case 1: tile_pieces<0, true, kImgFull>(lds, v, pc, lane, ShiftPrep<1>{v, b, lane, li, ll}); break;
-        case 2: tile_pieces<0, true, kImgFull>(lds, v, pc, lane, ShiftPrep<2>{v, b, lane, li, ll}); break;
-        default: tile_pieces<0, true, kImgFull>(lds, v, pc, lane, ShiftPrep<3>{v, b, lane, li, ll}); break;
+        case 0: tile_pieces<0, true, kImgSplit>(lds, v, pc, lane, ShiftPrep<0>{v, b, lane, li, ll}); break;
+        case 1: tile_pieces<0, true, kImgSplit>(lds, v, pc, lane, ShiftPrep<1>{v, b, lane, li, ll}); break;
+        case 2: tile_pieces<0, true, kImgSplit>(lds, v, pc, lane, ShiftPrep<2>{v, b, lane, li, ll}); break;
+        default: tile_pieces<0, true, kImgSplit>(lds, v, pc, lane, ShiftPrep<3>{v, b, lane, li, ll}); break;
     }
     rtile_reduce(p, lds, out, t, pc, lane);
 }
@@ -262,7 +262,7 @@ __device__ __forceinline__ void run_ptile(const RParams &p, const uint8_t *lds, 
 // `g` (valid: it has one).
 __device__ __forceinline__ void run_gen_item(const RParams &p, const uint8_t *lds, const uint8_t *payload,
                                              uint32_t *out, const GenItem &g, bool valid, int lane) {
-    const uint32_t acc = gen_item_lin<true, kImgFull>(payload, lds, g, lane);
+    const uint32_t acc = gen_item_lin<true, kImgSplit>(payload, lds, g, lane);
     if (valid && (lane & 31) == 0)
         rstore(out, g.out, out_order(acc ^ (g.len >= 4 ? 0xffffffffu : p.c_small[g.len]), p.flags));
 }
@@ -462,7 +462,7 @@ static inline __device__ void collector(const RParams &p, int lane) {
 template <uint32_t kWaves, uint32_t kPhases, uint32_t kPer, bool GENERAL = false>
 __global__ __launch_bounds__(kWaves * 64, kWaves / 4) void resident_kernel(RParams p) {
     constexpr uint32_t kWorkers = kWaves - 1;
-    constexpr uint32_t kStage = kS4StageBytes;
+    constexpr uint32_t kStage = kS4SStageBytes;
     __shared__ __attribute__((aligned(16))) uint8_t lds[kStage + 4 * kRing];
     uint32_t *lcnt = reinterpret_cast<uint32_t *>(lds + kStage);  // per slot: this workgroup's workers done
     const int lane = int(threadIdx.x & 63u);
@@ -472,7 +472,7 @@ __global__ __launch_bounds__(kWaves * 64, kWaves / 4) void resident_kernel(RPara
     for (uint32_t i = wv; i < kChunks; i += kWaves) {
         const uint32_t c = i + rot < kChunks ? i + rot : i + rot - kChunks;
         __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void *)(p.table_s4 + c * 1024u + 16u * uint32_t(lane)),
+            (const __attribute__((address_space(1))) void *)(p.table_s4 + hdfs_crc::kS4SOff + c * 1024u + 16u * uint32_t(lane)),
             (__attribute__((address_space(3))) void *)(lds + c * 1024u), 16, 0, 0);
     }
     if (threadIdx.x < kRing) lcnt[threadIdx.x] = 0;

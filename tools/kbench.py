@@ -146,7 +146,8 @@ def main():
                                                     "GBps": round(extent / (min(tt) * 1e-6) / 1e9, 1)}
     for v in times:
         t = sorted(times[v])
-        res[v] = {"median_us": round(t[len(t) // 2], 2), "min_us": round(t[0], 2),
+        res[v] = {"median_us": round(t[len(t) // 2], 2), "min_us": round(t[0], 2), "max_us": round(t[-1], 2),
+                  "rounds_us": [round(x, 2) for x in times[v]],
                   "GBps_median": round(nbytes / (t[len(t) // 2] * 1e-6) / 1e9, 1),
                   "GBps_best": round(nbytes / (t[0] * 1e-6) / 1e9, 1)}
     print(json.dumps({"config": args.config, "workload": workload, "bytes": nbytes, "variants": res}))
