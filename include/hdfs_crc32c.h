@@ -343,6 +343,79 @@ int crc32c_blocks_stats(const crc32c_blocks *q, uint64_t *flushes, uint64_t *blo
 int crc32c_blocks_destroy(crc32c_blocks *q);
 int crc32c_blocks_create_resident(crc32c_plan *plan, uint32_t idle_us, crc32c_blocks **out);
 
+/* ---------------------------------------------------------------------------
+ * 3c. Many blocks verified in one launch, with one verdict per block (the
+ * read side of 3b).
+ *
+ * A reader that holds a file's blocks in device memory asks "which replica
+ * block is corrupt, and which byte range do I fetch again?".  One
+ * crc32c_plan_verify_bitmap call per block is bound by the launch path
+ * (4.0-4.3 us per 4 MiB block) and a CRC32C_DEVICE_ADDRESSES plan over all
+ * of them answers with one count and one index for the whole set.
+ *
+ * crc32c_plan_verify_blocks: `plan` describes ONE block's packets, as for
+ * crc32c_plan_exec_blocks; n = crc32c_plan_nchecksums(plan).  Block b's
+ * payload is at dev_payloads[b] (a HOST array of nblocks device pointers,
+ * consumed before the call returns; any alignment -- a block off 16-byte
+ * alignment takes the shifted loads), its expected checksums are
+ * dev_expected[b * n .. (b + 1) * n): ONE contiguous device array in the
+ * plan's stored order (the reader chooses where it copies them).  Block b's
+ * verdict goes to dev_verdicts[b]:
+ *   mismatches  mismatching checksums of the block (at most 2^31 - 1 are
+ *               counted); bit 31 = CRC32C_VERIFY_OVERLAP as in
+ *               crc32c_plan_verify: the verdicts of the block's launch (its
+ *               32 blocks) are indeterminate, run the call again;
+ *   first_bad   lowest mismatching checksum index, counted from the block's
+ *               first checksum (0xffffffff: none);
+ *   last_bad    highest one (0xffffffff: none) -- the bytes to fetch again
+ *               are [first_bad * bpc, (last_bad + 1) * bpc) of the block for
+ *               a plan of one bpc with checksums in payload order;
+ *   reserved    0.
+ * A clean block reads {0, 0xffffffff, 0xffffffff, 0}.
+ *
+ * dev_work: crc32c_plan_verify_blocks_work_bytes(plan, nblocks) bytes of the
+ * caller's device scratch, 4-byte aligned, written by the call:
+ *   u32 [0, W), W = ceil(nblocks * n / 32): the mismatch bitmap over all
+ *       nblocks * n checksums, block b's bits at [b * n, (b + 1) * n) (bit
+ *       k = bit k % 32 of word k / 32), so a caller reads per-chunk bits
+ *       there;
+ *   u32 [W + 2 g, W + 2 g + 2), g < ceil(nblocks / 32): launch g's
+ *       {mismatches | overlap bit, lowest bad index counted from block 32 g's
+ *       first checksum}, as crc32c_plan_verify's dev_result.
+ * Neither dev_work nor dev_verdicts needs clearing: every word of both is
+ * written by every call (no memset is issued, nothing is built or uploaded
+ * per call, and the call may be captured into a HIP graph; a replay is
+ * idempotent).  One verify launch per 32 blocks -- launch g compares blocks
+ * 32 g .. 32 g + 31 and clears its own whole words of the bitmap (32 n bits
+ * are whole words, so launches never share one) -- then one verdict launch
+ * (section 6d) over the bitmap, all on `stream`.  The verify launches share
+ * the plan's slot like every verify launch of the plan (above).
+ *
+ * Everything is checked before the first launch: the call launches all or
+ * nothing.  -EINVAL (crc32c_last_error says why) for: plan == NULL; a
+ * CRC32C_DEVICE_ADDRESSES or crc32c_plan_create_buffers plan; a plan with
+ * work items other than tiles or with no tile -- a packet tail under 4
+ * bytes, a packet tail of at most 512 bytes behind chunks of 512 * 2^k bytes
+ * (a block whose last bpc-512 chunk is short), a packet shorter than one
+ * chunk, bpc outside [4, 8192]: such plans have no multi-block form (the
+ * plans crc32c_plan_exec_blocks runs one launch per block): stay with one
+ * crc32c_plan_verify_bitmap per block (and crc32c_bitmap_verdicts over its
+ * bitmap); n > 2^27; payloads of one launch's 32 blocks more than 2^47 bytes
+ * apart; a NULL pointer; dev_expected, dev_verdicts or dev_work off 4-byte
+ * alignment.  nblocks == 0 or n == 0: 0, nothing written.
+ * Measured ("Reading with checksums").
+ * ------------------------------------------------------------------------- */
+typedef struct crc32c_block_verdict {
+    uint32_t mismatches; /* mismatching checksums in the cell; bit 31 = CRC32C_VERIFY_OVERLAP */
+    uint32_t first_bad;  /* lowest mismatching index, counted from the cell's first checksum; 0xffffffff if none */
+    uint32_t last_bad;   /* highest such index; 0xffffffff if none */
+    uint32_t reserved;   /* 0 */
+} crc32c_block_verdict;
+
+uint64_t crc32c_plan_verify_blocks_work_bytes(const crc32c_plan *plan, size_t nblocks);
+int crc32c_plan_verify_blocks(crc32c_plan *plan, const void *const *dev_payloads, const uint32_t *dev_expected,
+                              size_t nblocks, crc32c_block_verdict *dev_verdicts, void *dev_work, void *stream);
+
 /* One-shot device batch: builds a plan, runs it on `stream` and waits for it. */
 int crc32c_chunks_dev(crc32c_ctx *ctx, const crc32c_packet *pkts, size_t npkts, const void *dev_payload,
                       uint32_t *dev_out, uint32_t flags, void *stream);
@@ -681,6 +754,45 @@ int crc32c_composite_block_list(crc32c_ctx *ctx, const uint32_t *const *dev_sums
 int crc32c_plan_exec_blocks_composite(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs,
                                       size_t nblocks, uint32_t *dev_crcs, void *stream);
 int crc32c_plan_composite_shape(const crc32c_plan *plan, uint32_t *bpc, uint32_t *last_len);
+
+/* ---------------------------------------------------------------------------
+ * 6d. Per-cell verdicts from a mismatch bitmap.
+ *
+ * A bitmap of nsums bits in the layout crc32c_plan_verify_bitmap writes (bit
+ * k = bit k % 32 of word k / 32) cut into cells of crc_per_cell bits -- cell
+ * i covers bits [i * crc_per_cell, min((i + 1) * crc_per_cell, nsums)), the
+ * last cell ragged -- gives one crc32c_block_verdict (section 3c) per cell:
+ * the set bits counted (at most 2^31 - 1; bit 31 is 0 here), the lowest and
+ * the highest set bit counted from the cell's first bit (0xffffffff: none),
+ * reserved = 0.  crc32c_md5_nblocks(nsums, crc_per_cell) verdicts.  The
+ * bitmap may come from any crc32c_plan_verify_bitmap launch earlier on the
+ * same stream (cell = a packet, a stripe cell, a block); a reader fetches
+ * [first_bad * bpc, (last_bad + 1) * bpc) of the cell again.
+ *
+ * Pointers need 4-byte alignment and no more.  The bitmap is read up to word
+ * ceil(nsums / 32) - 1 and not a byte further; bits of that word at or past
+ * nsums are ignored, and so are a neighbour cell's bits in a shared word.
+ * nsums == 0: 0, nothing written.  -EINVAL (crc32c_last_error says why),
+ * nothing written or launched: ctx == NULL (device call), crc_per_cell == 0
+ * with nsums > 0, a NULL pointer with cells present, a pointer off 4-byte
+ * alignment.
+ *
+ * crc32c_bitmap_verdicts_host: bitmap and verdicts in host memory (a bitmap
+ * that was copied back anyway).
+ * crc32c_bitmap_verdicts: both in device memory; asynchronous on `stream`,
+ * no host-side state, capturable into a HIP graph.  ONE launch for any cell
+ * count, no atomics and no clearing pass: every verdict is written by
+ * exactly one lane, so a replay is idempotent.  Cells of at most 128 bits
+ * run one lane per cell; larger cells one wave per cell (coalesced loads of
+ * 64 words, then a 64-lane sum / min / max).  A cell is never split over
+ * waves: one very large cell (a 128 MiB block at bpc 512 is 262 144 bits =
+ * 128 loads per lane) is one wave's loop, which costs its latency and leaves
+ * the rest of the device idle when it is the only cell.
+ * ------------------------------------------------------------------------- */
+int crc32c_bitmap_verdicts_host(const uint32_t *bad_bits, uint64_t nsums, uint32_t crc_per_cell,
+                                crc32c_block_verdict *verdicts);
+int crc32c_bitmap_verdicts(crc32c_ctx *ctx, const uint32_t *dev_bad_bits, uint64_t nsums, uint32_t crc_per_cell,
+                           crc32c_block_verdict *dev_verdicts, void *stream);
 
 /* The read side ("next" row 1): the packet stream a DataNode sends for
  * OP_READ_BLOCK with sendChecksums, per packet PLEN (u32 BE) | HLEN (u16 BE)

@@ -132,6 +132,18 @@ void crc32c_debug_composite_geometry(crc32c_debug_composite_geom *out);
  * *last_len, or -EINVAL when the batch is not of the shape.  No GPU. */
 int crc32c_debug_packets_composite_shape(const crc32c_packet *pkts, size_t npkts, uint32_t *bpc, uint32_t *last_len);
 
+/* The verdict kernel's geometry (csrc/crc32c_verdicts.hip, hdfs_crc32c.h
+ * section 6d; host only, no GPU): a cell of at most lane_max_cell bits is
+ * read by one lane, a larger one by one wave of `lanes` lanes; a workgroup is
+ * waves_per_workgroup waves; a launch has at most grid_cap workgroups and
+ * strides over the cells beyond them (past grid_cap * waves_per_workgroup *
+ * lanes cells in the lane form, grid_cap * waves_per_workgroup in the wave
+ * form).  The tests place their sizes from these. */
+typedef struct crc32c_debug_verdict_geom {
+    uint32_t lane_max_cell, lanes, waves_per_workgroup, grid_cap;
+} crc32c_debug_verdict_geom;
+void crc32c_debug_verdict_geometry(crc32c_debug_verdict_geom *out);
+
 /* ---- 2. libhdfs_crc32c_debug.so only ---- */
 
 /* Launch of a plan with an explicit kernel variant (0 = production; see

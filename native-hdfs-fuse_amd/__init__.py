@@ -256,6 +256,11 @@ def _bind(L):
         "crc32c_plan_composite_shape": (i32, [vp, vp, vp]),
         "crc32c_debug_composite_geometry": (None, [vp]),
         "crc32c_debug_packets_composite_shape": (i32, [vp, sz, vp, vp]),
+        "crc32c_bitmap_verdicts_host": (i32, [vp, u64, u32, vp]),
+        "crc32c_bitmap_verdicts": (i32, [vp, vp, u64, u32, vp, vp]),
+        "crc32c_plan_verify_blocks_work_bytes": (u64, [vp, sz]),
+        "crc32c_plan_verify_blocks": (i32, [vp, vp, vp, sz, vp, vp, vp]),
+        "crc32c_debug_verdict_geometry": (None, [vp]),
         "crc32c_verify_host": (ctypes.c_int64, [vp, vp, vp, sz, vp, u32, vp]),
         "crc32c_debug_affine_constants": (None, [u32, vp, vp]),
         "hdfs_crc32": (u32, [u32, vp, sz]),
@@ -426,6 +431,29 @@ def debug_composite_geometry() -> dict:
     return dict(zip(["run", "lanes", "waves_per_workgroup", "split_above"], (int(x) for x in g)))
 
 
+# crc32c_block_verdict: one per cell of a mismatch bitmap / per block of Plan.verify_blocks
+BLOCK_VERDICT_DTYPE = np.dtype([("mismatches", "<u4"), ("first_bad", "<u4"), ("last_bad", "<u4"), ("reserved", "<u4")])
+
+
+def bitmap_verdicts_host(bits: np.ndarray, nsums: int, crc_per_cell: int) -> np.ndarray:
+    """crc32c_bitmap_verdicts_host: a mismatch bitmap in host memory (u32 words, bit k = bit k % 32 of
+    word k // 32) cut into cells of crc_per_cell bits -> one BLOCK_VERDICT_DTYPE record per cell (count,
+    lowest and highest set bit counted from the cell's first bit, 0xffffffff when none)."""
+    bits = np.ascontiguousarray(bits, dtype=np.uint32)
+    ncells = md5_nblocks(nsums, crc_per_cell)
+    out = np.zeros(max(ncells, 1), BLOCK_VERDICT_DTYPE)
+    _check(lib().crc32c_bitmap_verdicts_host(_np_ptr(bits) if bits.size else None, nsums, crc_per_cell,
+                                             _np_ptr(out)), "crc32c_bitmap_verdicts_host")
+    return out[:ncells]
+
+
+def debug_verdict_geometry() -> dict:
+    """crc32c_debug_verdict_geometry: the verdict kernel's lane_max_cell, lanes, waves_per_workgroup, grid_cap."""
+    g = np.zeros(4, np.uint32)
+    lib().crc32c_debug_verdict_geometry(_np_ptr(g))
+    return dict(zip(["lane_max_cell", "lanes", "waves_per_workgroup", "grid_cap"], (int(x) for x in g)))
+
+
 def debug_packets_composite_shape(pkts):
     """The (bpc, last_len) crc32c_plan_create would record for the batch, or None when it is not of the
     composite shape (no GPU)."""
@@ -565,6 +593,14 @@ class Context:
                                                  ctypes.c_void_p(_stream_handle(stream, {}))),
                "crc32c_composite_block_list")
 
+    def bitmap_verdicts(self, dev_bad_bits: int, nsums: int, crc_per_cell: int, dev_verdicts: int, stream=0) -> None:
+        """crc32c_bitmap_verdicts: a mismatch bitmap in device memory (what Plan.verify wrote to
+        dev_bad_bits) cut into cells of crc_per_cell bits -> one crc32c_block_verdict (16 bytes,
+        BLOCK_VERDICT_DTYPE) per cell to dev_verdicts; one launch, asynchronous on ``stream``."""
+        _check(lib().crc32c_bitmap_verdicts(self.handle, ctypes.c_void_p(dev_bad_bits), nsums, crc_per_cell,
+                                            ctypes.c_void_p(dev_verdicts),
+                                            ctypes.c_void_p(_stream_handle(stream, {}))), "crc32c_bitmap_verdicts")
+
 
 class Plan:
     """Device-resident batch plan (crc32c_plan): build once, execute many.
@@ -624,6 +660,23 @@ class Plan:
         outs = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_outs])
         _check(lib().crc32c_plan_exec_blocks(self.handle, pays, outs, n, ctypes.c_void_p(stream)),
                "crc32c_plan_exec_blocks")
+
+    def verify_blocks_work_bytes(self, nblocks: int) -> int:
+        """crc32c_plan_verify_blocks_work_bytes: the bytes of device scratch verify_blocks needs for nblocks
+        blocks (the bitmap over nblocks * nchecksums checksums, then two u32 per launch of 32 blocks)."""
+        return int(lib().crc32c_plan_verify_blocks_work_bytes(self.handle, nblocks))
+
+    def verify_blocks(self, dev_payloads, dev_expected: int, dev_verdicts: int, dev_work: int, stream=0) -> None:
+        """crc32c_plan_verify_blocks: this plan (one block's shape) compared on every block -- block b's
+        payload at dev_payloads[b], its expected checksums at dev_expected + 4 * b * nchecksums -- one
+        verify launch per 32 blocks and one verdict launch: a crc32c_block_verdict (BLOCK_VERDICT_DTYPE)
+        per block to dev_verdicts, the mismatch bitmap of all blocks at the start of dev_work."""
+        stream = self._stream(stream)
+        n = len(dev_payloads)
+        pays = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_payloads])
+        _check(lib().crc32c_plan_verify_blocks(self.handle, pays, ctypes.c_void_p(dev_expected), n,
+                                               ctypes.c_void_p(dev_verdicts), ctypes.c_void_p(dev_work),
+                                               ctypes.c_void_p(stream)), "crc32c_plan_verify_blocks")
 
     def exec_blocks_md5(self, dev_payloads, dev_outs, dev_md5: int, stream=0) -> None:
         """crc32c_plan_exec_blocks_md5: exec_blocks, then each block's MD5 (16 bytes to dev_md5 + 16 i)

@@ -967,6 +967,7 @@ int crc32c_ctx_create(int device, crc32c_ctx **out) {
     HIP_TRY(preload_plan_kernels());
     HIP_TRY(preload_md5_kernels());
     HIP_TRY(preload_composite_kernels());
+    HIP_TRY(preload_verdict_kernels());
     c->host_pool.pinned = true;
     HIP_TRY(hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking));
     for (int ty = 0; ty < 2; ++ty) {
@@ -1191,6 +1192,81 @@ extern "C" {
 int crc32c_plan_exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs,
                             size_t nblocks, void *stream) {
     return exec_blocks(plan, dev_payloads, dev_outs, nblocks, static_cast<hipStream_t>(stream), nullptr);
+}
+
+// The work area of crc32c_plan_verify_blocks (hdfs_crc32c.h section 3c): the
+// bitmap's words, then two u32 per launch.
+static uint64_t verify_blocks_bitmap_words(const crc32c_plan *plan, size_t nblocks) {
+    return (uint64_t(nblocks) * plan->nchecksums + 31) / 32;
+}
+
+uint64_t crc32c_plan_verify_blocks_work_bytes(const crc32c_plan *plan, size_t nblocks) {
+    if (!plan) return 0;
+    const uint64_t launches = (uint64_t(nblocks) + kMaxLaunchBlocks - 1) / kMaxLaunchBlocks;
+    return 4 * (verify_blocks_bitmap_words(plan, nblocks) + 2 * launches);
+}
+
+int crc32c_plan_verify_blocks(crc32c_plan *plan, const void *const *dev_payloads, const uint32_t *dev_expected,
+                              size_t nblocks, crc32c_block_verdict *dev_verdicts, void *dev_work, void *stream) {
+    if (!plan) return fail(-EINVAL, "plan == NULL");
+    if (plan->absolute)
+        return fail(-EINVAL, "a multi-block verify takes a plan of one block's shape, not device addresses or buffers");
+    const uint64_t n = plan->nchecksums;
+    if (n == 0 || nblocks == 0) return 0;
+    const DevicePlan &dp = plan->dp;
+    if (dp.ngen || dp.nseg || dp.nconst || dp.ntiles == 0)
+        return fail(-EINVAL, "a plan with items other than tiles (a short packet tail, a packet under one chunk, bpc "
+                             "outside [4, 8192]) has no multi-block verify: use crc32c_plan_verify_bitmap per block");
+    // (a launch's bitmap indices and tile count stay below 2^32)
+    if (n > (1ull << 27) || uint64_t(kMaxLaunchBlocks) * dp.ntiles > UINT32_MAX)
+        return fail(-EINVAL, "a block of %llu checksums is more than a multi-block verify holds (2^27)",
+                    (unsigned long long)n);
+    if (!dev_payloads || !dev_expected || !dev_verdicts || !dev_work)
+        return fail(-EINVAL, "payloads/expected/verdicts/work == NULL");
+    if ((uintptr_t(dev_expected) | uintptr_t(dev_verdicts) | uintptr_t(dev_work)) & 3u)
+        return fail(-EINVAL, "expected/verdicts/work not 4-byte aligned");
+    // Launch g: blocks 32 g .. 32 g + 31, payload deltas from the lowest
+    // (16-byte aligned) address among them, below 2^47 (tile offsets keep a
+    // tail length in bits 48-63).  All checked before the first launch.
+    for (size_t i = 0; i < nblocks; i += kMaxLaunchBlocks) {
+        uintptr_t plo = UINTPTR_MAX, phi = 0;
+        for (size_t k = i; k < std::min<size_t>(nblocks, i + kMaxLaunchBlocks); ++k) {
+            if (!dev_payloads[k]) return fail(-EINVAL, "block %zu: payload NULL", k);
+            const uintptr_t pp = uintptr_t(dev_payloads[k]) & ~uintptr_t(15);
+            plo = std::min(plo, pp), phi = std::max(phi, pp);
+        }
+        if (phi - plo >= (uintptr_t(1) << 47))
+            return fail(-EINVAL, "blocks %zu..: payloads more than 2^47 bytes apart in one launch", i);
+    }
+    DeviceGuard guard(plan->ctx->device);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    uint32_t *bitmap = static_cast<uint32_t *>(dev_work);
+    uint32_t *results = bitmap + verify_blocks_bitmap_words(plan, nblocks);
+    for (size_t i = 0, g = 0; i < nblocks; i += kMaxLaunchBlocks, ++g) {
+        const size_t j = std::min<size_t>(nblocks, i + kMaxLaunchBlocks);
+        uintptr_t plo = UINTPTR_MAX;
+        for (size_t k = i; k < j; ++k) plo = std::min(plo, uintptr_t(dev_payloads[k]) & ~uintptr_t(15));
+        KParams p = plan_params(plan, reinterpret_cast<const void *>(plo), nullptr);
+        p.nblocks = uint32_t(j - i);
+        p.block_tiles = dp.ntiles;
+        p.ntiles = uint32_t(uint64_t(j - i) * dp.ntiles);
+        for (size_t k = i; k < j; ++k) {
+            BlockRef &b = p.blocks[k - i];
+            b.payload_delta = uint64_t(uintptr_t(dev_payloads[k]) - plo);
+            b.out_delta = uint32_t((k - i) * n);  // expected values and bitmap bits of the launch's block k - i
+            b.reserved = 0;
+            if (b.payload_delta & 15u) p.general |= kGeneralShift;  // (shifted loads for blocks off 16-byte alignment)
+        }
+        // 32 n bits are whole words: launch g's bitmap starts at word g n and
+        // its own clear (verify_init) covers exactly its words
+        p.expect = dev_expected + uint64_t(i) * n;
+        p.result = results + 2 * g;
+        p.bad_bits = bitmap + g * n;
+        p.bad_words = uint32_t((uint64_t(j - i) * n + 31) / 32);
+        if (int rc = launch_plan(plan, p, s)) return rc;
+    }
+    return launch_verdicts(plan->ctx, bitmap, uint64_t(nblocks) * n, uint32_t(n), dev_verdicts, results,
+                           kMaxLaunchBlocks, s);
 }
 
 int crc32c_plan_verify(crc32c_plan *plan, const void *dev_payload, const uint32_t *dev_expected,

@@ -232,6 +232,14 @@ int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *co
 hipError_t preload_md5_kernels();
 // The same for the composite-CRC kernels (crc32c_composite.hip).
 hipError_t preload_composite_kernels();
+// The same for the verdict kernels (crc32c_verdicts.hip).
+hipError_t preload_verdict_kernels();
+// crc32c_bitmap_verdicts over checked arguments (nsums > 0, crc_per_cell >
+// 0, aligned pointers).  group_results (optional): cell i also takes bit 31
+// of group_results[2 (i / cells_per_group)] (crc32c_plan_verify_blocks).
+int launch_verdicts(const crc32c_ctx *ctx, const uint32_t *dev_bad_bits, uint64_t nsums, uint32_t crc_per_cell,
+                    crc32c_block_verdict *dev_verdicts, const uint32_t *group_results, uint32_t cells_per_group,
+                    hipStream_t s);
 // A destroyed plan's blocks back to the pools once its launches are done.
 void release_plan_blocks(crc32c_plan *plan);
 // Context teardown: waits for the releases, frees every pooled block.
