@@ -840,6 +840,97 @@ typedef struct crc32c_frames_result {
 int crc32c_verify_frames_host(crc32c_ctx *ctx, const void *frames, size_t bytes, uint32_t bpc,
                               uint64_t chunk_offset, uint32_t flags, crc32c_frames_result *res);
 
+/* ---------------------------------------------------------------------------
+ * 7. AES/CTR/NoPadding: HDFS encrypted transport and encryption zones.
+ *
+ * A NameNode with dfs.encrypt.data.transfer announces it in the
+ * FsServerDefaultsProto the reference already fetches (proto/hdfs.proto:237,
+ * encryptDataTransfer; the reference lists the feature as missing,
+ * README.md:44-50); since Hadoop 2.6 the negotiated cipher is
+ * AES/CTR/NoPadding, and the same codec encrypts file contents in encryption
+ * zones (keystream position = file offset).  One definition for host and
+ * device:
+ *   ctr(n)       = the 16-byte IV plus n as a 128-bit BIG-ENDIAN addition with
+ *                  carry through all 16 bytes, wrapping mod 2^128 (Hadoop's
+ *                  AesCtrCryptoCodec.calculateIV; OpenSSL's CTR);
+ *   keystream(s) = AES_K(ctr(s >> 4))[s & 15];
+ *   out[i]       = in[i] ^ keystream(stream_off + i).
+ * Encrypting and decrypting are the same call.  Keys of 128, 192 and 256 bits
+ * (10, 12, 14 rounds).
+ *
+ * hdfs_aes_ctr is plain caller-owned data (no allocation, no handle):
+ * hdfs_aes_ctr_init expands the key on the host (rk[4 r + c] = column c of
+ * round key r as a big-endian word); -EINVAL for another key size or a NULL
+ * argument.  hdfs_aes_ctr_counter is ctr(block_index).  hdfs_aes_ctr_xor is
+ * the host path (a portable table implementation; any alignment, in == out
+ * allowed).  Key bytes never appear in an error text.
+ *
+ * Device forms: asynchronous on `stream` (a hipStream_t, NULL = the default
+ * stream), no host-side state, capturable into a HIP graph.  src, dst and
+ * stream_off may have ANY alignment and any phase mod 16, independently of
+ * each other.  dst == src (in place) is allowed; any other overlap of a
+ * segment's source with a destination is the caller's error (-EINVAL where
+ * a single segment shows it).  Only bytes of [dst, dst + len) are written --
+ * 16-byte stores inside, byte stores at a segment's unaligned ends, never a
+ * read-modify-write of neighbouring bytes -- and src is read no further than
+ * the next 16-byte boundary past its last byte (nor before the one at or
+ * below its first), as in section 3.
+ *
+ * hdfs_aes_ctr_xor_strided_dev: segment i is seg_len bytes at
+ * src + i * src_stride, written to dst + i * dst_stride, at stream offset
+ * stream_off0 + i * stream_stride.  ONE launch for any nsegs, nothing built
+ * or uploaded.  nsegs == 1 is the contiguous case (a block of an
+ * encryption-zone file); nsegs > 1 the uniform packets of a block on the
+ * wire (data 64 KiB apart in memory, 65536 + prefix apart in the stream).
+ * hdfs_aes_ctr_xor_list_dev: ragged sets (a trimmed first packet, a short
+ * last one).  segs is a HOST array consumed before the call returns; the
+ * references and the round keys ride in the kernel arguments: one launch per
+ * HDFS_AES_LIST_MAX_SEGMENTS segments.  A segment with len == 0 may have NULL
+ * pointers.
+ *
+ * Both return -EINVAL (crc32c_last_error says why; nothing is launched) for
+ * ctx or c == NULL, c->rounds not 10, 12 or 14, a NULL pointer with bytes to
+ * process, a stream offset + length beyond 2^64, a segment whose source and
+ * destination overlap without being equal; -ENODEV for ctx == NULL on a host
+ * without a GPU.  seg_len == 0 or nsegs == 0: 0, nothing written.
+ *
+ * hdfs_aes_wire_segments (host only): the stream layout of a batch on an
+ * encrypted transfer -- prefix 0, data 0, prefix 1, data 1, ... from
+ * stream_base -- from the batch's packets and the prefix_off array
+ * crc32c_frame_packets returns (npkts + 1 entries).  Per packet i:
+ * prefix_stream_off[i] = the stream offset of its prefix (the host encrypts
+ * those 31 + 4 n bytes with hdfs_aes_ctr_xor: 0.8 % of the stream), and
+ * data_segs[i] = {src_base + payload_off, dst_base + payload_off, the stream
+ * offset of its data, len}; a zero-length packet yields a zero-length
+ * segment.  Returns npkts, or -EINVAL (cap < npkts, NULL arrays, a stream
+ * beyond 2^64).
+ * ------------------------------------------------------------------------- */
+#define HDFS_AES_LIST_MAX_SEGMENTS 64u
+typedef struct hdfs_aes_ctr {
+    uint32_t rk[60];
+    uint8_t iv[16];
+    uint32_t rounds;
+    uint32_t reserved[3];
+} hdfs_aes_ctr;
+int hdfs_aes_ctr_init(hdfs_aes_ctr *c, const uint8_t *key, uint32_t key_bits, const uint8_t iv[16]);
+void hdfs_aes_ctr_counter(const uint8_t iv[16], uint64_t block_index, uint8_t out[16]);
+int hdfs_aes_ctr_xor(const hdfs_aes_ctr *c, uint64_t stream_off, const void *in, void *out, size_t len);
+
+typedef struct hdfs_aes_segment {
+    const void *src;
+    void *dst;
+    uint64_t stream_off;
+    uint64_t len;
+} hdfs_aes_segment;
+int hdfs_aes_ctr_xor_strided_dev(crc32c_ctx *ctx, const hdfs_aes_ctr *c, const void *src, void *dst,
+                                 uint64_t seg_len, uint64_t nsegs, uint64_t src_stride, uint64_t dst_stride,
+                                 uint64_t stream_off0, uint64_t stream_stride, void *stream);
+int hdfs_aes_ctr_xor_list_dev(crc32c_ctx *ctx, const hdfs_aes_ctr *c, const hdfs_aes_segment *segs, size_t nsegs,
+                              void *stream);
+int64_t hdfs_aes_wire_segments(const crc32c_packet *pkts, size_t npkts, const uint64_t *prefix_off,
+                               uint64_t stream_base, const void *src_base, void *dst_base,
+                               hdfs_aes_segment *data_segs, uint64_t *prefix_stream_off, size_t cap);
+
 /* Last error text of the calling thread (static storage, never NULL). */
 const char *crc32c_last_error(void);
 

@@ -144,6 +144,22 @@ typedef struct crc32c_debug_verdict_geom {
 } crc32c_debug_verdict_geom;
 void crc32c_debug_verdict_geometry(crc32c_debug_verdict_geom *out);
 
+/* The AES/CTR kernel's geometry (csrc/aes_ctr.hip, hdfs_crc32c.h section 7;
+ * host only, no GPU).  A segment is cut at the 16-byte boundaries of its
+ * DESTINATION: a lane takes lane_bytes of consecutive windows, a wave
+ * wave_bytes, a workgroup workgroup_bytes per pass over its grid-stride loop;
+ * a segment whose first byte is off a boundary spills into one more unit than
+ * its length alone fills.  list_max_segments = HDFS_AES_LIST_MAX_SEGMENTS,
+ * the segments of one list launch.  These are the units of a launch that
+ * fills the device: a launch of at most lanes_per_cu * CUs windows (16 bytes
+ * each) gives a lane one window, one of at most twice that two, and the
+ * units shrink to a quarter / a half.  The tests place their sizes from
+ * these. */
+typedef struct crc32c_debug_aes_geom {
+    uint32_t lane_bytes, wave_bytes, workgroup_bytes, list_max_segments, lanes_per_cu;
+} crc32c_debug_aes_geom;
+void crc32c_debug_aes_geometry(crc32c_debug_aes_geom *out);
+
 /* ---- 2. libhdfs_crc32c_debug.so only ---- */
 
 /* Launch of a plan with an explicit kernel variant (0 = production; see

@@ -300,6 +300,13 @@ def _bind(L):
         "crc32c_debug_select_build": (i32, [u32, u32, u32, u32, u32, i32, u32, ctypes.POINTER(DebugBuild)]),
         "crc32c_debug_plan_launch_info": (i32, [vp, vp, i32, ctypes.POINTER(DebugLaunchInfo)]),
         "crc32c_debug_packets_flags": (i32, [vp, sz, i32, ctypes.POINTER(u32), ctypes.POINTER(i32)]),
+        "hdfs_aes_ctr_init": (i32, [vp, vp, u32, vp]),
+        "hdfs_aes_ctr_counter": (None, [vp, u64, vp]),
+        "hdfs_aes_ctr_xor": (i32, [vp, u64, vp, vp, sz]),
+        "hdfs_aes_ctr_xor_strided_dev": (i32, [vp, vp, vp, vp, u64, u64, u64, u64, u64, u64, vp]),
+        "hdfs_aes_ctr_xor_list_dev": (i32, [vp, vp, vp, sz, vp]),
+        "hdfs_aes_wire_segments": (ctypes.c_int64, [vp, sz, vp, u64, vp, vp, vp, vp, sz]),
+        "crc32c_debug_aes_geometry": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -454,6 +461,94 @@ def debug_verdict_geometry() -> dict:
     return dict(zip(["lane_max_cell", "lanes", "waves_per_workgroup", "grid_cap"], (int(x) for x in g)))
 
 
+# --- 7. AES/CTR/NoPadding (encrypted transfer, encryption zones) -----------
+AES_LIST_MAX_SEGMENTS = 64  # HDFS_AES_LIST_MAX_SEGMENTS: segments per launch of Context.aes_ctr_xor_list
+# hdfs_aes_segment: src / dst device addresses (0 allowed where len == 0)
+AES_SEGMENT_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("stream_off", "<u8"), ("len", "<u8")])
+
+
+class _AesCtrStruct(ctypes.Structure):
+    _fields_ = [("rk", ctypes.c_uint32 * 60), ("iv", ctypes.c_uint8 * 16), ("rounds", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 3)]
+
+
+class AesCtr:
+    """hdfs_aes_ctr: an expanded AES key (16, 24 or 32 bytes) and a 16-byte IV.  ``xor`` is the host
+    path (encrypting and decrypting are the same call); the device forms are
+    ``Context.aes_ctr_xor_strided`` and ``Context.aes_ctr_xor_list``."""
+
+    def __init__(self, key: bytes, iv: bytes):
+        self.c = _AesCtrStruct()
+        self.init(key, iv)
+
+    def init(self, key: bytes, iv: bytes) -> None:
+        key, iv = bytes(key), bytes(iv)
+        if len(iv) != 16:
+            raise ValueError("the IV is 16 bytes (%d given)" % len(iv))
+        kb = (ctypes.c_uint8 * max(len(key), 1)).from_buffer_copy(key or b"\0")
+        ib = (ctypes.c_uint8 * 16).from_buffer_copy(iv)
+        _check(lib().hdfs_aes_ctr_init(ctypes.byref(self.c), kb, 8 * len(key), ib), "hdfs_aes_ctr_init")
+
+    @property
+    def rounds(self) -> int:
+        return int(self.c.rounds)
+
+    @property
+    def handle(self):
+        return ctypes.byref(self.c)
+
+    @staticmethod
+    def counter(iv: bytes, block_index: int) -> bytes:
+        """hdfs_aes_ctr_counter: ctr(block_index) = IV + block_index, 128-bit big-endian (calculateIV)."""
+        ib = (ctypes.c_uint8 * 16).from_buffer_copy(bytes(iv))
+        out = (ctypes.c_uint8 * 16)()
+        lib().hdfs_aes_ctr_counter(ib, block_index, out)
+        return bytes(out)
+
+    def xor(self, stream_off: int, data, out: np.ndarray | None = None) -> np.ndarray:
+        """hdfs_aes_ctr_xor: data ^ keystream(stream_off ...) on the host.  ``data`` is bytes or a
+        uint8 array (views at any alignment are used where they lie); ``out`` (optional, may be
+        ``data`` itself) receives the result."""
+        a = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data
+        if a.dtype != np.uint8 or (a.size and not a.flags.c_contiguous):
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+        if out is None:
+            out = np.empty(a.size, np.uint8)
+        if out.dtype != np.uint8 or out.size != a.size or (out.size and not out.flags.c_contiguous):
+            raise ValueError("out must be a contiguous uint8 array of the input's size")
+        _check(lib().hdfs_aes_ctr_xor(self.handle, stream_off, ctypes.c_void_p(a.ctypes.data if a.size else 0),
+                                      ctypes.c_void_p(out.ctypes.data if out.size else 0), a.size),
+               "hdfs_aes_ctr_xor")
+        return out
+
+
+def aes_wire_segments(pkts, prefix_off, stream_base: int = 0, src_base: int = 0, dst_base: int = 0):
+    """hdfs_aes_wire_segments: the stream layout of a batch on an encrypted transfer (prefix 0, data 0,
+    prefix 1, ... from stream_base) from the packets and the offsets ``frame_packets`` returns:
+    (prefix stream offsets[npkts], data segments[npkts] as AES_SEGMENT_DTYPE)."""
+    pkts = as_packets(pkts)
+    offs = np.ascontiguousarray(prefix_off, dtype=np.uint64)
+    if offs.size != pkts.size + 1:
+        raise ValueError("prefix_off has npkts + 1 entries")
+    segs = np.zeros(max(pkts.size, 1), AES_SEGMENT_DTYPE)
+    pre = np.zeros(max(pkts.size, 1), np.uint64)
+    n = int(lib().hdfs_aes_wire_segments(_np_ptr(pkts), pkts.size, _np_ptr(offs), stream_base,
+                                         ctypes.c_void_p(src_base), ctypes.c_void_p(dst_base), _np_ptr(segs),
+                                         _np_ptr(pre), pkts.size))
+    if n < 0:
+        _check(n, "hdfs_aes_wire_segments")
+    return pre[:n], segs[:n]
+
+
+def debug_aes_geometry() -> dict:
+    """crc32c_debug_aes_geometry: the AES/CTR kernel's lane_bytes, wave_bytes, workgroup_bytes,
+    list_max_segments, lanes_per_cu."""
+    g = np.zeros(5, np.uint32)
+    lib().crc32c_debug_aes_geometry(_np_ptr(g))
+    return dict(zip(["lane_bytes", "wave_bytes", "workgroup_bytes", "list_max_segments", "lanes_per_cu"],
+                    (int(x) for x in g)))
+
+
 def debug_packets_composite_shape(pkts):
     """The (bpc, last_len) crc32c_plan_create would record for the batch, or None when it is not of the
     composite shape (no GPU)."""
@@ -600,6 +695,31 @@ class Context:
         _check(lib().crc32c_bitmap_verdicts(self.handle, ctypes.c_void_p(dev_bad_bits), nsums, crc_per_cell,
                                             ctypes.c_void_p(dev_verdicts),
                                             ctypes.c_void_p(_stream_handle(stream, {}))), "crc32c_bitmap_verdicts")
+
+
+    def aes_ctr_xor_strided(self, aes: "AesCtr", src: int, dst: int, seg_len: int, nsegs: int = 1,
+                            src_stride: int = 0, dst_stride: int = 0, stream_off: int = 0, stream_stride: int = 0,
+                            stream=0) -> None:
+        """hdfs_aes_ctr_xor_strided_dev: segment i = seg_len bytes at src + i * src_stride, XOR-ed with
+        the keystream from stream_off + i * stream_stride on, to dst + i * dst_stride (dst == src: in
+        place); any alignment; ONE launch, asynchronous on ``stream``.  nsegs == 1: a contiguous range."""
+        _check(lib().hdfs_aes_ctr_xor_strided_dev(self.handle, aes.handle if aes is not None else None,
+                                                  ctypes.c_void_p(src), ctypes.c_void_p(dst), seg_len, nsegs,
+                                                  src_stride, dst_stride, stream_off, stream_stride,
+                                                  ctypes.c_void_p(_stream_handle(stream, {}))),
+               "hdfs_aes_ctr_xor_strided_dev")
+
+    def aes_ctr_xor_list(self, aes: "AesCtr", segs, stream=0) -> None:
+        """hdfs_aes_ctr_xor_list_dev: ragged segments [(src, dst, stream_off, len), ...] (or an
+        AES_SEGMENT_DTYPE array; addresses 0 allowed where len == 0); one launch per
+        AES_LIST_MAX_SEGMENTS segments, asynchronous on ``stream``."""
+        if not (isinstance(segs, np.ndarray) and segs.dtype == AES_SEGMENT_DTYPE):
+            segs = np.array([tuple(int(v) for v in s) for s in segs], dtype=AES_SEGMENT_DTYPE)
+        segs = np.ascontiguousarray(segs)
+        _check(lib().hdfs_aes_ctr_xor_list_dev(self.handle, aes.handle if aes is not None else None,
+                                               _np_ptr(segs) if segs.size else None, segs.size,
+                                               ctypes.c_void_p(_stream_handle(stream, {}))),
+               "hdfs_aes_ctr_xor_list_dev")
 
 
 class Plan:
