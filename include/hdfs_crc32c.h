@@ -931,6 +931,108 @@ int64_t hdfs_aes_wire_segments(const crc32c_packet *pkts, size_t npkts, const ui
                                uint64_t stream_base, const void *src_base, void *dst_base,
                                hdfs_aes_segment *data_segs, uint64_t *prefix_stream_off, size_t cap);
 
+/* ---------------------------------------------------------------------------
+ * 8. Erasure coding: HDFS 3 striped (EC) block groups.
+ *
+ * A file in an erasure-coded directory is cut into cells; every stripe of k
+ * data cells gets m parity cells, and each of the k + m internal blocks of a
+ * block group goes to its own DataNode with its own checksums.  One
+ * definition for host and device:
+ *   field      GF(2^8) with the reducing polynomial x^8+x^4+x^3+x^2+1 (0x11d),
+ *              the field of ISA-L and of Hadoop's GF256 (Hadoop's Java and
+ *              native RS coders interoperate); addition is XOR;
+ *   generator  [I_k ; P]; for HDFS_EC_RS P[r][j] = inv((k + r) ^ j), r < m,
+ *              j < k (Hadoop's RSUtil.genCauchyMatrix, ISA-L's
+ *              gf_gen_cauchy1_matrix); for HDFS_EC_XOR m = 1, P[0][j] = 1;
+ *   decoding   from k distinct surviving unit indices in [0, k + m) take the
+ *              matching generator rows as a k x k matrix S; an erased data
+ *              unit e < k is row e of S^-1 applied to the survivors, an erased
+ *              parity unit e is P[e - k] * S^-1.  The code is MDS, so the
+ *              recovery rows are unique and every correct implementation
+ *              gives the same bytes.
+ * k <= 16 and m <= 4 cover every built-in policy (RS-6-3, RS-3-2, RS-10-4,
+ * XOR-2-1).  Compatibility with Hadoop rests on this definition being
+ * Hadoop's; it has not been checked against a Hadoop build.
+ *
+ * hdfs_ec_matrix is plain caller-owned data (no allocation, no handle):
+ * out[r][t] = sum_j coef[r][j] * in[j][t] for r < n_out, j < n_in.
+ * hdfs_ec_encode_matrix fills P (n_in = k, n_out = m): -EINVAL for k == 0,
+ * k > 16, m == 0, m > 4, HDFS_EC_XOR with m != 1, another codec, NULL.
+ * hdfs_ec_decode_matrix fills the recovery rows (n_in = k, n_out = n_erased):
+ * column i multiplies surviving unit valid[i], row r rebuilds unit erased[r];
+ * -EINVAL also for an index >= k + m, a duplicate in either list, an index in
+ * both lists, n_erased == 0 or > 4.
+ *
+ * Striping (Hadoop's StripedBlockUtil).  A block group of `len` bytes in file
+ * order is cut into cells of `cell` bytes; cell i belongs to stripe i / k and
+ * to data block i % k, at block offset (i / k) * cell.  In the last stripe,
+ * missing cells and the missing part of a short cell count as zeros; the
+ * parity of stripe s covers min(cell, len - s k cell) bytes (the length of the
+ * stripe's cell 0), so every parity block has the length of data block 0.
+ * hdfs_ec_group_layout writes the k + m internal block lengths (-EINVAL for
+ * cell == 0, bad k / m, NULL).
+ * hdfs_ec_block_packets lists the crc32c_packets of data block `block` (< k)
+ * over the FILE-ORDER buffer, so that a plain crc32c_plan checksums the block
+ * where it lies: payload_off steps through the block's cells at stride k cell,
+ * the lengths are those of crc32c_packetize(block length, 0, packetsize, bpc)
+ * without the final empty packet, and the checksums are packed from out_idx0
+ * on.  Returns the packet count (pkts == NULL: only that), or -EINVAL unless
+ * cell % packetsize == 0 and packetsize % bpc == 0 (also: block >= k, cap too
+ * small, zero arguments).
+ *
+ * hdfs_ec_apply is the host path (portable nibble tables; any alignment):
+ * in[j] == NULL means a unit of zeros (an absent cell of a short stripe).
+ *
+ * Device forms: asynchronous on `stream` (a hipStream_t, NULL = the default
+ * stream), no host-side state, capturable into a HIP graph; ONE launch each,
+ * the pointers and the matrix ride in the kernel arguments, nothing is built
+ * or uploaded.  The pointer ARRAYS are host arrays consumed before the call
+ * returns; the units are device memory.  Every pointer may have any alignment
+ * independently of the others.  Only bytes of [out, out + len) are written --
+ * 16-byte stores where an output shares output 0's phase mod 16, narrower
+ * ones where it does not and at the unaligned ends, never a read-modify-write
+ * of neighbouring bytes -- and an input is read no further than the next
+ * 16-byte boundary past its last byte (nor before the one at or below its
+ * first).
+ * hdfs_ec_apply_dev: out[r][t] = sum_j coef[r][j] * in[j][t], t < len;
+ * dev_in[j] == NULL means zeros.
+ * hdfs_ec_encode_striped_dev: every stripe of a block group of `len` bytes at
+ * `src` in file order; parity row r of stripe s goes to dev_parity[r] + s *
+ * cell; one launch for any number of stripes; a partial last stripe follows
+ * the striping rules above (mx->n_in = k, mx->n_out = m).  Any cell > 0 is
+ * accepted, but a stripe costs at least one 64-lane wave unit (1 KiB of
+ * parity per row), and a cell that is no multiple of 16 puts every stripe's
+ * parity at another phase: cells below 1 KiB or off a multiple of 16 are
+ * correct and slow (HDFS's cells are 1 MiB).
+ * Both return -EINVAL (crc32c_last_error says why; nothing is launched) for
+ * ctx or mx == NULL, n_in == 0 or > 16, n_out == 0 or > 4, a NULL array or a
+ * NULL output (or src) with bytes to process, an output that overlaps an
+ * input or another output, cell == 0; -ENODEV for ctx == NULL on a host
+ * without a GPU.  len == 0: 0, nothing written.
+ * ------------------------------------------------------------------------- */
+#define HDFS_EC_RS 0
+#define HDFS_EC_XOR 1
+#define HDFS_EC_MAX_DATA 16u
+#define HDFS_EC_MAX_PARITY 4u
+typedef struct hdfs_ec_matrix {
+    uint32_t n_in, n_out;
+    uint8_t coef[4][16];
+    uint32_t reserved[2];
+} hdfs_ec_matrix;
+uint8_t hdfs_gf256_mul(uint8_t a, uint8_t b);
+uint8_t hdfs_gf256_inv(uint8_t a);
+int hdfs_ec_encode_matrix(int codec, uint32_t k, uint32_t m, hdfs_ec_matrix *out);
+int hdfs_ec_decode_matrix(int codec, uint32_t k, uint32_t m, const uint32_t *valid, const uint32_t *erased,
+                          uint32_t n_erased, hdfs_ec_matrix *out);
+int hdfs_ec_group_layout(uint64_t len, uint32_t k, uint32_t m, uint64_t cell, uint64_t *block_len);
+int64_t hdfs_ec_block_packets(uint64_t len, uint32_t k, uint64_t cell, uint32_t block, uint32_t packetsize,
+                              uint32_t bpc, uint64_t out_idx0, crc32c_packet *pkts, size_t cap);
+int hdfs_ec_apply(const hdfs_ec_matrix *mx, const void *const *in, void *const *out, size_t len);
+int hdfs_ec_apply_dev(crc32c_ctx *ctx, const hdfs_ec_matrix *mx, const void *const *dev_in, void *const *dev_out,
+                      uint64_t len, void *stream);
+int hdfs_ec_encode_striped_dev(crc32c_ctx *ctx, const hdfs_ec_matrix *mx, const void *src, uint64_t len,
+                               uint64_t cell, void *const *dev_parity, void *stream);
+
 /* Last error text of the calling thread (static storage, never NULL). */
 const char *crc32c_last_error(void);
 

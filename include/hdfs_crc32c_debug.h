@@ -160,6 +160,24 @@ typedef struct crc32c_debug_aes_geom {
 } crc32c_debug_aes_geom;
 void crc32c_debug_aes_geometry(crc32c_debug_aes_geom *out);
 
+/* The erasure-coding kernel's geometry (csrc/ec_rs.hip, hdfs_crc32c.h section
+ * 8; host only, no GPU).  A unit is cut at the 16-byte boundaries of OUTPUT 0:
+ * a lane takes one window of lane_bytes, a wave wave_bytes (a wave unit), a
+ * workgroup workgroup_bytes per pass over its grid-stride loop; a unit whose
+ * output 0 is off a boundary spills into one more window than its length
+ * alone fills.  The nibble tables are held table_copies times in LDS,
+ * lds_bytes_per_input bytes per input of the matrix, so a CU holds
+ * min(max_workgroups_per_cu, lds_bytes_per_cu / (lds_bytes_per_input * n_in))
+ * workgroups, and a launch has at most that many times the CUs, of
+ * waves_per_workgroup waves each: up to that many wave units every workgroup
+ * runs one wave, up to waves_per_workgroup times that many no wave loops.
+ * The tests place their sizes from these. */
+typedef struct crc32c_debug_ec_geom {
+    uint32_t lane_bytes, wave_bytes, workgroup_bytes, waves_per_workgroup, table_copies, lds_bytes_per_input,
+        lds_bytes_per_cu, max_workgroups_per_cu;
+} crc32c_debug_ec_geom;
+void crc32c_debug_ec_geometry(crc32c_debug_ec_geom *out);
+
 /* ---- 2. libhdfs_crc32c_debug.so only ---- */
 
 /* Launch of a plan with an explicit kernel variant (0 = production; see

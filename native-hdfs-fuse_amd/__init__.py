@@ -307,6 +307,16 @@ def _bind(L):
         "hdfs_aes_ctr_xor_list_dev": (i32, [vp, vp, vp, sz, vp]),
         "hdfs_aes_wire_segments": (ctypes.c_int64, [vp, sz, vp, u64, vp, vp, vp, vp, sz]),
         "crc32c_debug_aes_geometry": (None, [vp]),
+        "hdfs_gf256_mul": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8]),
+        "hdfs_gf256_inv": (ctypes.c_uint8, [ctypes.c_uint8]),
+        "hdfs_ec_encode_matrix": (i32, [i32, u32, u32, vp]),
+        "hdfs_ec_decode_matrix": (i32, [i32, u32, u32, vp, vp, u32, vp]),
+        "hdfs_ec_group_layout": (i32, [u64, u32, u32, u64, vp]),
+        "hdfs_ec_block_packets": (ctypes.c_int64, [u64, u32, u64, u32, u32, u32, u64, vp, sz]),
+        "hdfs_ec_apply": (i32, [vp, vp, vp, sz]),
+        "hdfs_ec_apply_dev": (i32, [vp, vp, vp, vp, u64, vp]),
+        "hdfs_ec_encode_striped_dev": (i32, [vp, vp, vp, u64, u64, vp, vp]),
+        "crc32c_debug_ec_geometry": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -549,6 +559,133 @@ def debug_aes_geometry() -> dict:
                     (int(x) for x in g)))
 
 
+# --- 8. Erasure coding (striped block groups) -------------------------------
+EC_RS, EC_XOR = 0, 1  # HDFS_EC_RS, HDFS_EC_XOR
+EC_MAX_DATA, EC_MAX_PARITY = 16, 4
+
+
+class _EcMatrixStruct(ctypes.Structure):
+    _fields_ = [("n_in", ctypes.c_uint32), ("n_out", ctypes.c_uint32), ("coef", (ctypes.c_uint8 * 16) * 4),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+def gf256_mul(a: int, b: int) -> int:
+    """hdfs_gf256_mul: a * b in GF(2^8) mod 0x11d."""
+    return int(lib().hdfs_gf256_mul(a, b))
+
+
+def gf256_inv(a: int) -> int:
+    """hdfs_gf256_inv: the multiplicative inverse in GF(2^8) mod 0x11d (0 -> 0)."""
+    return int(lib().hdfs_gf256_inv(a))
+
+
+def _unit_ptrs(units, n: int, what: str):
+    """A (void *)[n] of addresses (None / 0 = NULL) and n itself; None for no array at all."""
+    if units is None:
+        return None
+    units = list(units)
+    if len(units) != n:
+        raise ValueError("%s: %d units for a matrix of %d" % (what, len(units), n))
+    return (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(int(u) if u else 0) for u in units])
+
+
+class EcMatrix:
+    """hdfs_ec_matrix: out[r] = sum_j coef[r][j] * in[j] over GF(2^8).  ``EcMatrix.encode`` is the parity
+    part of a scheme, ``EcMatrix.decode`` the recovery rows of an erasure pattern; ``apply`` is the host
+    path, ``Context.ec_apply`` / ``Context.ec_encode_striped`` the device forms."""
+
+    def __init__(self, rows=None):
+        self.c = _EcMatrixStruct()
+        if rows is not None:
+            rows = [list(r) for r in rows]
+            self.c.n_out, self.c.n_in = len(rows), len(rows[0]) if rows else 0
+            for r, row in enumerate(rows[:4]):
+                for j, v in enumerate(row[:16]):
+                    self.c.coef[r][j] = v
+
+    @classmethod
+    def encode(cls, k: int, m: int, codec: int = EC_RS) -> "EcMatrix":
+        mx = cls()
+        _check(lib().hdfs_ec_encode_matrix(codec, k, m, ctypes.byref(mx.c)), "hdfs_ec_encode_matrix")
+        return mx
+
+    @classmethod
+    def decode(cls, k: int, m: int, valid, erased, codec: int = EC_RS) -> "EcMatrix":
+        """Column i multiplies surviving unit valid[i] (k of them), row r rebuilds unit erased[r]."""
+        mx = cls()
+        v = np.ascontiguousarray(valid, dtype=np.uint32)
+        e = np.ascontiguousarray(erased, dtype=np.uint32)
+        if v.size != k:
+            raise ValueError("valid lists k = %d surviving units (%d given)" % (k, v.size))
+        _check(lib().hdfs_ec_decode_matrix(codec, k, m, _np_ptr(v), _np_ptr(e) if e.size else None, e.size,
+                                           ctypes.byref(mx.c)), "hdfs_ec_decode_matrix")
+        return mx
+
+    @property
+    def n_in(self) -> int:
+        return int(self.c.n_in)
+
+    @property
+    def n_out(self) -> int:
+        return int(self.c.n_out)
+
+    @property
+    def rows(self) -> list:
+        return [[int(self.c.coef[r][j]) for j in range(self.n_in)] for r in range(self.n_out)]
+
+    @property
+    def handle(self):
+        return ctypes.byref(self.c)
+
+    def apply_ptrs(self, ins, outs, length: int) -> None:
+        """hdfs_ec_apply over raw host addresses (None / 0 in ``ins`` = a unit of zeros)."""
+        _check(lib().hdfs_ec_apply(self.handle, _unit_ptrs(ins, self.n_in, "inputs"),
+                                   _unit_ptrs(outs, self.n_out, "outputs"), length), "hdfs_ec_apply")
+
+    def apply(self, units) -> list:
+        """hdfs_ec_apply: the n_out output units of n_in input units (uint8 arrays of one length, or
+        None for a unit of zeros)."""
+        units = [None if u is None else np.ascontiguousarray(u, dtype=np.uint8) for u in units]
+        sizes = {u.size for u in units if u is not None}
+        if len(sizes) > 1:
+            raise ValueError("units of different lengths")
+        n = sizes.pop() if sizes else 0
+        outs = [np.zeros(n, np.uint8) for _ in range(self.n_out)]
+        if n:
+            self.apply_ptrs([None if u is None else u.ctypes.data for u in units], [o.ctypes.data for o in outs], n)
+        return outs
+
+
+def ec_group_layout(length: int, k: int, m: int, cell: int) -> list:
+    """hdfs_ec_group_layout: the k + m internal block lengths of a striped block group of ``length`` bytes."""
+    out = np.zeros(k + m if 0 < k <= 16 and 0 < m <= 4 else 20, np.uint64)
+    _check(lib().hdfs_ec_group_layout(length, k, m, cell, _np_ptr(out)), "hdfs_ec_group_layout")
+    return [int(x) for x in out[:k + m]]
+
+
+def ec_block_packets(length: int, k: int, cell: int, block: int, packetsize: int = 65536, bpc: int = 512,
+                     out_idx0: int = 0) -> np.ndarray:
+    """hdfs_ec_block_packets: the packets of data block ``block`` over the file-order buffer of a striped
+    block group (payload_off steps through the block's cells at stride k * cell)."""
+    n = int(lib().hdfs_ec_block_packets(length, k, cell, block, packetsize, bpc, out_idx0, None, 0))
+    if n < 0:
+        _check(n, "hdfs_ec_block_packets")
+    pk = np.zeros(max(n, 1), PACKET_DTYPE)
+    n = int(lib().hdfs_ec_block_packets(length, k, cell, block, packetsize, bpc, out_idx0, _np_ptr(pk), n))
+    if n < 0:
+        _check(n, "hdfs_ec_block_packets")
+    return pk[:n]
+
+
+def debug_ec_geometry() -> dict:
+    """crc32c_debug_ec_geometry: the erasure-coding kernel's lane_bytes, wave_bytes, workgroup_bytes,
+    waves_per_workgroup, table_copies, lds_bytes_per_input, lds_bytes_per_cu, max_workgroups_per_cu."""
+    g = np.zeros(8, np.uint32)
+    lib().crc32c_debug_ec_geometry(_np_ptr(g))
+    return dict(zip(["lane_bytes", "wave_bytes", "workgroup_bytes", "waves_per_workgroup", "table_copies",
+                     "lds_bytes_per_input", "lds_bytes_per_cu", "max_workgroups_per_cu"], (int(x) for x in g)))
+
+
 def debug_packets_composite_shape(pkts):
     """The (bpc, last_len) crc32c_plan_create would record for the batch, or None when it is not of the
     composite shape (no GPU)."""
@@ -720,6 +857,25 @@ class Context:
                                                _np_ptr(segs) if segs.size else None, segs.size,
                                                ctypes.c_void_p(_stream_handle(stream, {}))),
                "hdfs_aes_ctr_xor_list_dev")
+
+
+    def ec_apply(self, mx: "EcMatrix", dev_in, dev_out, length: int, stream=0) -> None:
+        """hdfs_ec_apply_dev: out[r][t] = sum_j coef[r][j] * in[j][t] for t < length over device units
+        (addresses; None / 0 in ``dev_in`` = zeros); any alignment; ONE launch, asynchronous on ``stream``."""
+        n_in, n_out = (mx.n_in, mx.n_out) if mx is not None else (len(dev_in or ()), len(dev_out or ()))
+        _check(lib().hdfs_ec_apply_dev(self.handle, mx.handle if mx is not None else None,
+                                       _unit_ptrs(dev_in, n_in, "inputs"), _unit_ptrs(dev_out, n_out, "outputs"),
+                                       length, ctypes.c_void_p(_stream_handle(stream, {}))), "hdfs_ec_apply_dev")
+
+    def ec_encode_striped(self, mx: "EcMatrix", src: int, length: int, cell: int, dev_parity, stream=0) -> None:
+        """hdfs_ec_encode_striped_dev: every stripe of a block group of ``length`` bytes at ``src`` in file
+        order; parity row r of stripe s goes to dev_parity[r] + s * cell; ONE launch."""
+        n_out = mx.n_out if mx is not None else len(dev_parity or ())
+        _check(lib().hdfs_ec_encode_striped_dev(self.handle, mx.handle if mx is not None else None,
+                                                ctypes.c_void_p(src), length, cell,
+                                                _unit_ptrs(dev_parity, n_out, "parity units"),
+                                                ctypes.c_void_p(_stream_handle(stream, {}))),
+               "hdfs_ec_encode_striped_dev")
 
 
 class Plan:

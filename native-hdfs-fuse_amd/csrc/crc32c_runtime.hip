@@ -969,6 +969,7 @@ int crc32c_ctx_create(int device, crc32c_ctx **out) {
     HIP_TRY(preload_composite_kernels());
     HIP_TRY(preload_verdict_kernels());
     HIP_TRY(preload_aes_kernels());
+    HIP_TRY(preload_ec_kernels());
     c->host_pool.pinned = true;
     HIP_TRY(hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking));
     for (int ty = 0; ty < 2; ++ty) {

@@ -236,6 +236,8 @@ hipError_t preload_composite_kernels();
 hipError_t preload_verdict_kernels();
 // The same for the AES/CTR kernels (aes_ctr.hip).
 hipError_t preload_aes_kernels();
+// The same for the erasure-coding kernels (ec_rs.hip).
+hipError_t preload_ec_kernels();
 // crc32c_bitmap_verdicts over checked arguments (nsums > 0, crc_per_cell >
 // 0, aligned pointers).  group_results (optional): cell i also takes bit 31
 // of group_results[2 (i / cells_per_group)] (crc32c_plan_verify_blocks).
