@@ -160,6 +160,26 @@ typedef struct crc32c_debug_aes_geom {
 } crc32c_debug_aes_geom;
 void crc32c_debug_aes_geometry(crc32c_debug_aes_geom *out);
 
+/* How the AES/CTR entry points would size one launch on num_cu CUs (host
+ * only, no GPU; the entry points size their launches with the same
+ * functions): the 16-byte windows of the launch, its wave units, the windows a
+ * lane takes (1, 2 or lane_bytes / 16) and the workgroups launched.  The
+ * strided call is hdfs_aes_ctr_xor_strided_dev's from dst, seg_len, nsegs and
+ * dst_stride (nothing else enters the sizing; a call with nothing to do
+ * reports zeros); the list call is ONE launch of hdfs_aes_ctr_xor_list_dev,
+ * nsegs <= HDFS_AES_LIST_MAX_SEGMENTS (only dst and len of a segment are
+ * looked at).  -EINVAL for num_cu == 0, out == NULL, more list segments than
+ * one launch holds, or a strided call of more wave units than 2^64.  The GPU
+ * tests assert with these that a launch took the path they name. */
+typedef struct crc32c_debug_aes_launch {
+    uint64_t windows, wave_units;
+    uint32_t windows_per_lane, grid;
+} crc32c_debug_aes_launch;
+int crc32c_debug_aes_strided_launch_info(uint32_t num_cu, const void *dst, uint64_t seg_len, uint64_t nsegs,
+                                         uint64_t dst_stride, crc32c_debug_aes_launch *out);
+int crc32c_debug_aes_list_launch_info(uint32_t num_cu, const hdfs_aes_segment *segs, size_t nsegs,
+                                      crc32c_debug_aes_launch *out);
+
 /* The erasure-coding kernel's geometry (csrc/ec_rs.hip, hdfs_crc32c.h section
  * 8; host only, no GPU).  A unit is cut at the 16-byte boundaries of OUTPUT 0:
  * a lane takes one window of lane_bytes, a wave wave_bytes (a wave unit), a

@@ -73,6 +73,15 @@ class DebugLaunchInfo(ctypes.Structure):
                 ("num_cu", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("build", DebugBuild)]
 
 
+class DebugAesLaunch(ctypes.Structure):
+    """crc32c_debug_aes_launch: the sizing of one AES/CTR launch."""
+    _fields_ = [("windows", ctypes.c_uint64), ("wave_units", ctypes.c_uint64),
+                ("windows_per_lane", ctypes.c_uint32), ("grid", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class Crc32cError(RuntimeError):
     def __init__(self, rc: int, msg: str):
         super().__init__("%s (rc=%d %s)" % (msg, rc, errno.errorcode.get(-rc, "?")))
@@ -307,6 +316,8 @@ def _bind(L):
         "hdfs_aes_ctr_xor_list_dev": (i32, [vp, vp, vp, sz, vp]),
         "hdfs_aes_wire_segments": (ctypes.c_int64, [vp, sz, vp, u64, vp, vp, vp, vp, sz]),
         "crc32c_debug_aes_geometry": (None, [vp]),
+        "crc32c_debug_aes_strided_launch_info": (i32, [u32, vp, u64, u64, u64, ctypes.POINTER(DebugAesLaunch)]),
+        "crc32c_debug_aes_list_launch_info": (i32, [u32, vp, sz, ctypes.POINTER(DebugAesLaunch)]),
         "hdfs_gf256_mul": (ctypes.c_uint8, [ctypes.c_uint8, ctypes.c_uint8]),
         "hdfs_gf256_inv": (ctypes.c_uint8, [ctypes.c_uint8]),
         "hdfs_ec_encode_matrix": (i32, [i32, u32, u32, vp]),
@@ -557,6 +568,31 @@ def debug_aes_geometry() -> dict:
     lib().crc32c_debug_aes_geometry(_np_ptr(g))
     return dict(zip(["lane_bytes", "wave_bytes", "workgroup_bytes", "list_max_segments", "lanes_per_cu"],
                     (int(x) for x in g)))
+
+
+def _aes_segments(segs) -> np.ndarray:
+    if not (isinstance(segs, np.ndarray) and segs.dtype == AES_SEGMENT_DTYPE):
+        segs = np.array([tuple(int(v) for v in s) for s in segs], dtype=AES_SEGMENT_DTYPE)
+    return np.ascontiguousarray(segs)
+
+
+def debug_aes_strided_launch_info(num_cu: int, dst: int, seg_len: int, nsegs: int = 1, dst_stride: int = 0) -> dict:
+    """crc32c_debug_aes_strided_launch_info: windows, wave_units, windows_per_lane and grid of the launch
+    Context.aes_ctr_xor_strided would make for these arguments on num_cu CUs (no GPU)."""
+    out = DebugAesLaunch()
+    _check(lib().crc32c_debug_aes_strided_launch_info(num_cu, ctypes.c_void_p(dst), seg_len, nsegs, dst_stride,
+                                                      ctypes.byref(out)), "crc32c_debug_aes_strided_launch_info")
+    return out.as_dict()
+
+
+def debug_aes_list_launch_info(num_cu: int, segs) -> dict:
+    """crc32c_debug_aes_list_launch_info: the same for ONE launch of Context.aes_ctr_xor_list (at most
+    AES_LIST_MAX_SEGMENTS segments, given as there)."""
+    segs = _aes_segments(segs)
+    out = DebugAesLaunch()
+    _check(lib().crc32c_debug_aes_list_launch_info(num_cu, _np_ptr(segs) if segs.size else None, segs.size,
+                                                   ctypes.byref(out)), "crc32c_debug_aes_list_launch_info")
+    return out.as_dict()
 
 
 # --- 8. Erasure coding (striped block groups) -------------------------------
@@ -850,9 +886,7 @@ class Context:
         """hdfs_aes_ctr_xor_list_dev: ragged segments [(src, dst, stream_off, len), ...] (or an
         AES_SEGMENT_DTYPE array; addresses 0 allowed where len == 0); one launch per
         AES_LIST_MAX_SEGMENTS segments, asynchronous on ``stream``."""
-        if not (isinstance(segs, np.ndarray) and segs.dtype == AES_SEGMENT_DTYPE):
-            segs = np.array([tuple(int(v) for v in s) for s in segs], dtype=AES_SEGMENT_DTYPE)
-        segs = np.ascontiguousarray(segs)
+        segs = _aes_segments(segs)
         _check(lib().hdfs_aes_ctr_xor_list_dev(self.handle, aes.handle if aes is not None else None,
                                                _np_ptr(segs) if segs.size else None, segs.size,
                                                ctypes.c_void_p(_stream_handle(stream, {}))),

@@ -275,11 +275,64 @@ uint64_t wave_units(uint64_t windows, uint32_t wpl) { return (windows + kLanes *
 // runs four waves per SIMD over one AES block each instead of one wave over
 // four (measured: 15.1 against 20.3 us).  Larger launches keep kWinPerLane,
 // which shares the extra AES block of a keystream phase != 0.
-uint32_t windows_per_lane(const crc32c_ctx *ctx, uint64_t windows) {
-    const uint64_t lanes = uint64_t(std::max(ctx->num_cu, 1)) * kWgPerCu * kThreads;
+uint32_t windows_per_lane(uint32_t num_cu, uint64_t windows) {
+    const uint64_t lanes = uint64_t(std::max(num_cu, 1u)) * kWgPerCu * kThreads;
     uint32_t wpl = 1;
     while (wpl < kWinPerLane && windows > lanes * wpl) wpl *= 2;
     return wpl;
+}
+
+uint32_t grid_for(uint32_t num_cu, uint64_t total) {
+    // (wave w of workgroup b takes units b + grid (w + kWaves i): a launch of few units still
+    // spreads over every CU, with fewer busy waves per workgroup)
+    return uint32_t(std::min<uint64_t>(total, uint64_t(std::max(num_cu, 1u)) * kWgPerCu));
+}
+
+uint32_t cus_of(const crc32c_ctx *ctx) { return uint32_t(std::max(ctx->num_cu, 1)); }
+
+// The sizing of one launch on num_cu CUs: what the entry points launch from and
+// what crc32c_debug_aes_*_launch_info report.
+struct Sizing {
+    uint64_t windows;  // of the whole launch (saturated)
+    uint64_t total;    // wave units of the launch
+    uint32_t wpl, grid;
+};
+
+// The strided form (seg_len, nsegs > 0; d: the first destination address);
+// *units_per_seg: wave units per segment.  False when the wave units of the
+// launch exceed 2^64.
+bool size_strided(uint32_t num_cu, uint64_t d, uint64_t seg_len, uint64_t nsegs, uint64_t dst_stride, Sizing *z,
+                  uint64_t *units_per_seg) {
+    // Every segment has the same destination phase when the stride keeps it;
+    // otherwise a segment may spill into one more window than its length fills.
+    const uint32_t a = (nsegs == 1 || (dst_stride & 15u) == 0) ? uint32_t(d & 15u) : 15u;
+    const uint64_t windows = windows_of(seg_len, a);
+    const bool many = __builtin_mul_overflow(nsegs, windows, &z->windows);
+    if (many) z->windows = ~0ull;
+    z->wpl = many ? kWinPerLane : windows_per_lane(num_cu, z->windows);
+    *units_per_seg = wave_units(windows, z->wpl);
+    if (__builtin_mul_overflow(nsegs, *units_per_seg, &z->total)) return false;
+    z->grid = grid_for(num_cu, z->total);
+    return true;
+}
+
+// One list launch over segs[0 .. n), n <= kListCap; first (kListCap + 1
+// entries, or NULL): the wave units before each of the kListCap slots, the
+// launch's total last.
+void size_list(uint32_t num_cu, const hdfs_aes_segment *segs, uint32_t n, Sizing *z, uint64_t *first) {
+    const auto windows_at = [&](uint32_t j) {
+        return j < n ? windows_of(segs[j].len, uint32_t(reinterpret_cast<uintptr_t>(segs[j].dst) & 15u)) : 0;
+    };
+    z->windows = 0;
+    for (uint32_t j = 0; j < n; ++j) z->windows += windows_at(j);
+    z->wpl = windows_per_lane(num_cu, z->windows);
+    z->total = 0;
+    for (uint32_t j = 0; j < kListCap; ++j) {
+        if (first) first[j] = z->total;
+        z->total += wave_units(windows_at(j), z->wpl);
+    }
+    if (first) first[kListCap] = z->total;
+    z->grid = grid_for(num_cu, z->total);
 }
 
 int check_key(const crc32c_ctx *ctx, const hdfs_aes_ctr *c, AesKey *k) {
@@ -308,12 +361,6 @@ int check_segment(uint64_t src, uint64_t dst, uint64_t so, uint64_t len, const c
     if (src != dst && src < dst + len && dst < src + len)
         return fail(-EINVAL, "%s %llu: source and destination overlap without being equal", what, (unsigned long long)idx);
     return 0;
-}
-
-uint32_t grid_for(const crc32c_ctx *ctx, uint64_t total) {
-    // (wave w of workgroup b takes units b + grid (w + kWaves i): a launch of few units still
-    // spreads over every CU, with fewer busy waves per workgroup)
-    return uint32_t(std::min<uint64_t>(total, uint64_t(std::max(ctx->num_cu, 1)) * kWgPerCu));
 }
 
 template <typename P, typename K10, typename K12, typename K14>
@@ -353,6 +400,37 @@ void crc32c_debug_aes_geometry(crc32c_debug_aes_geom *out) {
     out->lanes_per_cu = kWgPerCu * kThreads;
 }
 
+static void report(const Sizing &z, crc32c_debug_aes_launch *out) {
+    out->windows = z.windows;
+    out->wave_units = z.total;
+    out->windows_per_lane = z.wpl;
+    out->grid = z.grid;
+}
+
+int crc32c_debug_aes_strided_launch_info(uint32_t num_cu, const void *dst, uint64_t seg_len, uint64_t nsegs,
+                                         uint64_t dst_stride, crc32c_debug_aes_launch *out) {
+    if (num_cu == 0 || !out) return fail(-EINVAL, "crc32c_debug_aes_strided_launch_info: num_cu == 0 or out == NULL");
+    Sizing z{};
+    uint64_t units_per_seg;
+    if (seg_len != 0 && nsegs != 0 &&
+        !size_strided(num_cu, uint64_t(reinterpret_cast<uintptr_t>(dst)), seg_len, nsegs, dst_stride, &z, &units_per_seg))
+        return fail(-EINVAL, "%llu segments of %llu bytes are more than one launch holds", (unsigned long long)nsegs,
+                    (unsigned long long)seg_len);
+    report(z, out);
+    return 0;
+}
+
+int crc32c_debug_aes_list_launch_info(uint32_t num_cu, const hdfs_aes_segment *segs, size_t nsegs,
+                                      crc32c_debug_aes_launch *out) {
+    if (num_cu == 0 || !out) return fail(-EINVAL, "crc32c_debug_aes_list_launch_info: num_cu == 0 or out == NULL");
+    if (nsegs > kListCap) return fail(-EINVAL, "%llu segments: one launch holds %u", (unsigned long long)nsegs, kListCap);
+    if (nsegs != 0 && !segs) return fail(-EINVAL, "segs == NULL");
+    Sizing z;
+    size_list(num_cu, segs, uint32_t(nsegs), &z, nullptr);
+    report(z, out);
+    return 0;
+}
+
 int hdfs_aes_ctr_xor_strided_dev(crc32c_ctx *ctx, const hdfs_aes_ctr *c, const void *src, void *dst,
                                  uint64_t seg_len, uint64_t nsegs, uint64_t src_stride, uint64_t dst_stride,
                                  uint64_t stream_off0, uint64_t stream_stride, void *stream) {
@@ -369,16 +447,12 @@ int hdfs_aes_ctr_xor_strided_dev(crc32c_ctx *ctx, const hdfs_aes_ctr *c, const v
     if (__builtin_mul_overflow(last, stream_stride, &so_last) || __builtin_add_overflow(so_last, stream_off0, &so_last))
         return fail(-EINVAL, "segment %llu: stream offset + length exceeds 2^64", (unsigned long long)last);
     if (int rc = check_segment(s_last, d_last, so_last, seg_len, "segment", last)) return rc;
-    // Every segment has the same destination phase when the stride keeps it;
-    // otherwise a segment may spill into one more window than its length fills.
-    const uint32_t a = (nsegs == 1 || (dst_stride & 15u) == 0) ? uint32_t(d & 15u) : 15u;
-    const uint64_t windows = windows_of(seg_len, a);
-    uint64_t all_windows;
-    p.wpl = __builtin_mul_overflow(nsegs, windows, &all_windows) ? kWinPerLane : windows_per_lane(ctx, all_windows);
-    p.units_per_seg = wave_units(windows, p.wpl);
-    if (__builtin_mul_overflow(nsegs, p.units_per_seg, &p.total))
+    Sizing z;
+    if (!size_strided(cus_of(ctx), d, seg_len, nsegs, dst_stride, &z, &p.units_per_seg))
         return fail(-EINVAL, "%llu segments of %llu bytes are more than one launch holds", (unsigned long long)nsegs,
                     (unsigned long long)seg_len);
+    p.wpl = z.wpl;
+    p.total = z.total;
     p.src = s;
     p.dst = d;
     p.seg_len = seg_len;
@@ -387,8 +461,8 @@ int hdfs_aes_ctr_xor_strided_dev(crc32c_ctx *ctx, const hdfs_aes_ctr *c, const v
     p.so0 = stream_off0;
     p.so_stride = stream_stride;
     DeviceGuard guard(ctx->device);
-    return launch(c->rounds, grid_for(ctx, p.total), static_cast<hipStream_t>(stream), p,
-                  hdfs_aes_ctr_strided_kernel<10>, hdfs_aes_ctr_strided_kernel<12>, hdfs_aes_ctr_strided_kernel<14>);
+    return launch(c->rounds, z.grid, static_cast<hipStream_t>(stream), p, hdfs_aes_ctr_strided_kernel<10>,
+                  hdfs_aes_ctr_strided_kernel<12>, hdfs_aes_ctr_strided_kernel<14>);
 }
 
 int hdfs_aes_ctr_xor_list_dev(crc32c_ctx *ctx, const hdfs_aes_ctr *c, const hdfs_aes_segment *segs, size_t nsegs,
@@ -407,22 +481,19 @@ int hdfs_aes_ctr_xor_list_dev(crc32c_ctx *ctx, const hdfs_aes_ctr *c, const hdfs
     DeviceGuard guard(ctx->device);
     for (size_t i = 0; i < nsegs; i += kListCap) {
         const uint32_t n = uint32_t(std::min<size_t>(kListCap, nsegs - i));
-        uint64_t units = 0, windows = 0;
-        for (uint32_t j = 0; j < n; ++j) windows += windows_of(segs[i + j].len, uint32_t(reinterpret_cast<uintptr_t>(segs[i + j].dst) & 15u));
-        p.wpl = windows_per_lane(ctx, windows);
+        Sizing z;
+        size_list(cus_of(ctx), segs + i, n, &z, p.first);
+        p.wpl = z.wpl;
         for (uint32_t j = 0; j < kListCap; ++j) {
-            p.first[j] = units;
             const bool live = j < n && segs[i + j].len != 0;
             p.src[j] = live ? uint64_t(reinterpret_cast<uintptr_t>(segs[i + j].src)) : 0;
             p.dst[j] = live ? uint64_t(reinterpret_cast<uintptr_t>(segs[i + j].dst)) : 0;
             p.so[j] = live ? segs[i + j].stream_off : 0;
             p.len[j] = live ? segs[i + j].len : 0;
-            units += wave_units(windows_of(p.len[j], uint32_t(p.dst[j] & 15u)), p.wpl);
         }
-        p.first[kListCap] = units;
-        if (units == 0) continue;
-        if (int rc = launch(c->rounds, grid_for(ctx, units), static_cast<hipStream_t>(stream), p,
-                            hdfs_aes_ctr_list_kernel<10>, hdfs_aes_ctr_list_kernel<12>, hdfs_aes_ctr_list_kernel<14>))
+        if (z.total == 0) continue;
+        if (int rc = launch(c->rounds, z.grid, static_cast<hipStream_t>(stream), p, hdfs_aes_ctr_list_kernel<10>,
+                            hdfs_aes_ctr_list_kernel<12>, hdfs_aes_ctr_list_kernel<14>))
             return rc;
     }
     return 0;

@@ -65,6 +65,10 @@ class Dst:
         self.want[off:off + expected.size] = expected
         return self.base + off
 
+    def reset(self):
+        self.t.fill_(GUARD)
+        self.want[:] = GUARD
+
     def check(self, what=""):
         _torch().cuda.synchronize()
         got = self.t.cpu().numpy()
@@ -84,9 +88,10 @@ def _dev(a: np.ndarray):
 # ---- 1. the alignment cross ----------------------------------------------------------
 def test_alignment_cross(hdfs, gpu_ctx, data):
     """All 16 x 16 x 16 combinations of src % 16, dst % 16 and stream_off % 16 through the list form,
-    lengths cycling through 1, 15, 16, 17, 47, 100; every fifth segment at a stream offset below 16."""
+    lengths cycling through 1, 15, 16, 17, 31, 47, 100 (seven of them: coprime to 16, so every length
+    meets every value of every phase); every fifth segment at a stream offset below 16."""
     aes = hdfs.AesCtr(KEYS[128], IV)
-    lens = (1, 15, 16, 17, 47, 100)
+    lens = (1, 15, 16, 17, 31, 47, 100)
     slot = 160
     n = 16 * 16 * 16
     src_t, src = _dev(data[:n * slot])
@@ -138,6 +143,252 @@ def test_windows_per_lane_thresholds(hdfs, gpu_ctx, geom):
         d = dst.expect(16 + 3, aes.xor(so, big[6:6 + ln]))
         gpu_ctx.aes_ctr_xor_strided(aes, src + 6, d, ln, stream_off=so)
         dst.check("%d windows" % windows)
+
+
+# ---- 2b. two and four windows per lane ---------------------------------------------------------
+# A launch of more than lanes windows gives a lane 2 consecutive windows, one of more than 2 * lanes
+# lane_bytes / 16 of them: the kernel then carries a keystream block and a source chunk from window to
+# window, skips the extra block at keystream phase 0, and leaves the loop early where a segment ends
+# inside a lane.  Every launch below is just over its threshold, and every test asserts through
+# crc32c_debug_aes_*_launch_info -- the sizing the entry points launch from -- that it is.
+WPL = pytest.mark.parametrize("mode", ["two", "full"])
+
+
+def _wpl(geom, mode):
+    return 2 if mode == "two" else geom["lane_bytes"] // 16
+
+
+@pytest.fixture(scope="module")
+def cus():
+    return _torch().cuda.get_device_properties(0).multi_processor_count
+
+
+@pytest.fixture(scope="module")
+def lanes(geom, cus):
+    assert geom["lane_bytes"] // 16 > 2
+    return geom["lanes_per_cu"] * cus
+
+
+def _threshold(lanes, wpl):
+    """The most windows of a launch that still gives a lane fewer than wpl windows (wpl: 2, or lane_bytes / 16)."""
+    return lanes * wpl // 2
+
+
+@pytest.fixture(scope="module")
+def big(geom, lanes):
+    """Source bytes for a launch over the last threshold, on the host and (16-byte aligned) on the device."""
+    b = oracle.xorshift64_bytes(16 * _threshold(lanes, geom["lane_bytes"] // 16) + 3 * 65536, oracle.SEED + 3)
+    b.setflags(write=False)
+    t, addr = _dev(b)
+    return b, t, addr
+
+
+def _strided_info(hdfs, cus, wpl, dst, seg_len, nsegs=1, dst_stride=0):
+    info = hdfs.debug_aes_strided_launch_info(cus, dst, seg_len, nsegs, dst_stride)
+    assert info["windows_per_lane"] == wpl, (info, wpl)
+    return info
+
+
+@pytest.fixture(scope="module")
+def cross(hdfs, geom, data):
+    """The small segments of the phase cross, relative to their buffers -- (src offset, dst offset, stream
+    offset, length) -- and the expected image of their destination buffer.  With L = lane_bytes the lengths
+    end in each of a lane's windows and one window into the next lane, at one dst phase or another."""
+    L = geom["lane_bytes"]
+    lens = (1, 15, 16, 17, 47, 100, L // 2 + 1, L - 16, L - 15, L, L + 1, 2 * L - 1, 2 * L + 2)
+    assert len(set(lens)) == len(lens) and len(lens) % 2 == 1  # an odd count is coprime to 16
+    slot = (max(lens) + 15 + 16) // 16 * 16
+    n = 16 * 16 * 16
+    assert n * slot + 16 <= data.size
+    aes = hdfs.AesCtr(KEYS[128], IV)
+    want = np.full(n * slot + 32, GUARD, np.uint8)
+    segs, met = [], set()
+    for i in range(n):
+        sp, dp, op = i & 15, (i >> 4) & 15, (i >> 8) & 15
+        ln = lens[i % len(lens)]
+        so = op if i % 5 == 0 else ((i * 2654435761) % (1 << 44)) * 16 + op
+        s_off, d_off = i * slot + sp, 16 + i * slot + dp
+        want[d_off:d_off + ln] = aes.xor(so, data[s_off:s_off + ln])
+        segs.append((s_off, d_off, so, ln))
+        met |= {(ln, "src", sp), (ln, "dst", dp), (ln, "stream", op)}
+    assert len(met) == len(lens) * 3 * 16  # every length meets every value of every phase
+    want.setflags(write=False)
+    return segs, want
+
+
+@WPL
+def test_alignment_cross_many_windows_per_lane(hdfs, gpu_ctx, geom, cus, lanes, data, big, cross, mode):
+    """All 16 x 16 x 16 combinations of src % 16, dst % 16 and stream_off % 16 through list launches of 2
+    and of lane_bytes / 16 windows per lane: list_max_segments - 3 small segments per launch (the most
+    that leave room for the filler) and three filler segments of unequal length -- each many wave units
+    and a ragged tail, at phases of its own, first, in the middle and last in the list, so the kernel's
+    scan over first[] crosses multi-unit segments -- whose windows alone are one more than the
+    threshold.  The filler is compared on the device after every launch (and once on the host), the small
+    segments' buffer whole on the host after the last."""
+    torch = _torch()
+    wpl = _wpl(geom, mode)
+    aes = hdfs.AesCtr(KEYS[128], IV)
+    small, want = cross
+    big_b, big_t, big_addr = big
+    src_t, src = _dev(data[:want.size])
+    dst = Dst(want.size)
+    dst.want[:] = want
+    over = _threshold(lanes, wpl) + 1
+    counts = (over // 2, over // 3, over - over // 2 - over // 3)
+    # src % 16, dst % 16, stream_off % 16, bytes the segment ends before its last window does
+    shapes = ((5, 11, 2, 3), (0, 0, 0, 9), (7, 7, 12, 5))
+    fill = Dst(16 * over + 16 * len(counts) + 32)
+    fsegs, s_at, d_at = [], 0, 16
+    for k, (nw, (sp, dp, op, short)) in enumerate(zip(counts, shapes)):
+        ln = 16 * nw - dp - short
+        so = ((k + 1) << 40) + op
+        assert ln > 64 * geom["wave_bytes"] and s_at + sp + ln <= big_b.size
+        d = fill.expect(d_at + dp, aes.xor(so, big_b[s_at + sp:s_at + sp + ln]))
+        fsegs.append((big_addr + s_at + sp, d, so, ln))
+        assert hdfs.debug_aes_list_launch_info(cus, fsegs[-1:])["windows"] == nw
+        s_at, d_at = s_at + 16 * nw + 16, d_at + 16 * nw + 16
+    fill_want = torch.from_numpy(fill.want).cuda()
+    per = geom["list_max_segments"] - len(fsegs)
+    slot_windows = (small[1][1] - small[0][1]) // 16 + 1
+    for at in range(0, len(small), per):
+        chunk = [(src + s, dst.base + d, so, ln) for s, d, so, ln in small[at:at + per]]
+        segs = [fsegs[0]] + chunk[:per // 2] + [fsegs[1]] + chunk[per // 2:] + [fsegs[2]]
+        assert len(segs) <= geom["list_max_segments"]
+        info = hdfs.debug_aes_list_launch_info(cus, segs)
+        assert info["windows_per_lane"] == wpl and over < info["windows"] <= over + per * slot_windows, info
+        fill.t.fill_(GUARD)
+        gpu_ctx.aes_ctr_xor_list(aes, segs)
+        assert torch.equal(fill.t, fill_want), "the filler of the launch from segment %d on" % at
+    fill.check("the filler")
+    dst.check("alignment cross, %d windows per lane" % wpl)
+
+
+# src % 16, dst % 16, stream_off % 16: keystream phase (stream_off - dst) % 16, source phase (src - dst) % 16
+PHASE_CLASSES = {"aligned": (0, 0, 0), "source_off": (9, 5, 5), "keystream_off": (5, 5, 0), "both_off": (2, 13, 7)}
+
+
+@WPL
+@pytest.mark.parametrize("cls", list(PHASE_CLASSES))
+def test_phase_classes_and_tails(hdfs, gpu_ctx, geom, cus, lanes, big, mode, cls):
+    """Keystream phase and source phase each zero or not (all zero: src, dst and the stream offset on
+    16-byte boundaries, what a block write is), one contiguous call per length: the threshold's windows
+    and t more bytes, t ending 1 byte into, and at the end of, each of the next lane_bytes / 16 windows
+    (at 2 windows per lane: both windows of the last lane and of one more)."""
+    wpl = _wpl(geom, mode)
+    sp, dp, op = PHASE_CLASSES[cls]
+    assert (((op - dp) % 16 != 0), ((sp - dp) % 16 != 0)) == ("keystream" in cls or "both" in cls,
+                                                             "source" in cls or "both" in cls)
+    assert cls != "aligned" or (sp, dp, op) == (0, 0, 0)
+    aes = hdfs.AesCtr(KEYS[128], IV)
+    big_b, big_t, big_addr = big
+    thr = _threshold(lanes, wpl)
+    tails = [16 * k + d for k in range(geom["lane_bytes"] // 16) for d in (1, 16)]
+    so = (1 << 45) + 16 * 77 + op
+    top = 16 * thr - dp + max(tails)
+    ref = aes.xor(so, big_b[sp:sp + top])  # (one keystream: a shorter call's bytes are its prefix)
+    dst = Dst(16 + dp + top + 48)
+    for t in tails:
+        ln = 16 * thr - dp + t
+        info = _strided_info(hdfs, cus, wpl, dst.base + 16 + dp, ln)
+        assert info["windows"] == thr + (t + 15) // 16
+        dst.reset()
+        d = dst.expect(16 + dp, ref[:ln])
+        gpu_ctx.aes_ctr_xor_strided(aes, big_addr + sp, d, ln, stream_off=so)
+        dst.check("%s, %d windows per lane, %d bytes past the threshold" % (cls, wpl, t))
+
+
+def test_strided_ragged_full_windows_per_lane(hdfs, gpu_ctx, geom, cus, lanes, big):
+    """test_strided's ragged segments (no stride keeps a phase), just enough of them for lane_bytes / 16
+    windows per lane: a lane's windows end inside it wherever a segment ends."""
+    full = geom["lane_bytes"] // 16
+    aes = hdfs.AesCtr(KEYS[192], IV)
+    big_b, big_t, big_addr = big
+    seg_len, ss, ds, sos = 1000, 1024, 1003, 1543
+    so0 = (1 << 34) + 3
+    per_seg = hdfs.debug_aes_strided_launch_info(cus, 21, seg_len, 2, ds)["windows"] // 2
+    nsegs = _threshold(lanes, full) // per_seg + 1
+    assert (nsegs - 1) * ss + seg_len <= big_b.size
+    dst = Dst(nsegs * ds + 64)
+    _strided_info(hdfs, cus, full, dst.base + 21, seg_len, nsegs, ds)
+    assert hdfs.debug_aes_strided_launch_info(cus, dst.base + 21, seg_len, nsegs - 1, ds)["windows_per_lane"] < full
+    for i in range(nsegs):
+        dst.expect(21 + i * ds, aes.xor(so0 + i * sos, big_b[i * ss:i * ss + seg_len]))
+    gpu_ctx.aes_ctr_xor_strided(aes, big_addr, dst.base + 21, seg_len, nsegs, ss, ds, so0, sos)
+    dst.check("%d ragged segments" % nsegs)
+
+
+def test_strided_packets_full_windows_per_lane(hdfs, gpu_ctx, geom, cus, lanes, big):
+    """64 KiB packets with every address, stride and stream offset a multiple of 16 (keystream and source
+    phase 0 in every segment), just enough of them for lane_bytes / 16 windows per lane; the destinations
+    32 bytes apart, which must stay as they were."""
+    full = geom["lane_bytes"] // 16
+    aes = hdfs.AesCtr(KEYS[128], IV)
+    big_b, big_t, big_addr = big
+    seg_len, ss, ds, sos = 65536, 65536, 65536 + 32, 65536 + 48
+    so0 = 1 << 36
+    nsegs = _threshold(lanes, full) // (seg_len // 16) + 1
+    assert nsegs > 1 and nsegs * ss <= big_b.size
+    dst = Dst(nsegs * ds + 32)
+    info = _strided_info(hdfs, cus, full, dst.base + 16, seg_len, nsegs, ds)
+    assert info["windows"] == nsegs * (seg_len // 16)
+    assert hdfs.debug_aes_strided_launch_info(cus, dst.base + 16, seg_len, nsegs - 1, ds)["windows_per_lane"] < full
+    for i in range(nsegs):
+        dst.expect(16 + i * ds, aes.xor(so0 + i * sos, big_b[i * ss:(i + 1) * ss]))
+    gpu_ctx.aes_ctr_xor_strided(aes, big_addr, dst.base + 16, seg_len, nsegs, ss, ds, so0, sos)
+    dst.check("%d aligned packets" % nsegs)
+
+
+@WPL
+@pytest.mark.parametrize("bits", [192, 256])
+def test_key_sizes_many_windows_per_lane(hdfs, gpu_ctx, geom, cus, lanes, big, mode, bits):
+    """AES-192 and AES-256 (builds of their own) one window over the threshold.  Everything aligned, with
+    an IV whose carry from the low into the high 64 bits falls inside one lane -- after its 2nd of 4
+    windows (its 1st of 2); and an IV of all ones at stream offset 2^63 + 7 with src and dst off phase."""
+    wpl = _wpl(geom, mode)
+    big_b, big_t, big_addr = big
+    windows = _threshold(lanes, wpl) + 1
+    lane = 64 * 37 + 41  # (lane 41 of wave unit 37)
+    assert (lane + 1) * wpl <= windows
+    first_block = 1000
+    carried = first_block + lane * wpl + wpl // 2  # the first block whose counter has the carry
+    iv = IV[:8] + ((1 << 64) - carried).to_bytes(8, "big")
+    assert hdfs.AesCtr.counter(iv, carried - 1) == IV[:8] + b"\xff" * 8
+    assert hdfs.AesCtr.counter(iv, carried) == (int.from_bytes(IV[:8], "big") + 1).to_bytes(8, "big") + bytes(8)
+    ln = 16 * windows
+    dst = Dst(ln + 64)
+    aes = hdfs.AesCtr(KEYS[bits], iv)
+    d = dst.expect(16, aes.xor(16 * first_block, big_b[:ln]))
+    assert _strided_info(hdfs, cus, wpl, d, ln)["windows"] == windows
+    gpu_ctx.aes_ctr_xor_strided(aes, big_addr, d, ln, stream_off=16 * first_block)
+    dst.check("AES-%d, the carry in a lane of %d windows" % (bits, wpl))
+    aes = hdfs.AesCtr(KEYS[bits], b"\xff" * 16)
+    so = (1 << 63) + 7
+    ln = 16 * windows - 3 - 5
+    dst.reset()
+    d = dst.expect(16 + 3, aes.xor(so, big_b[6:6 + ln]))
+    assert _strided_info(hdfs, cus, wpl, d, ln)["windows"] == windows
+    gpu_ctx.aes_ctr_xor_strided(aes, big_addr + 6, d, ln, stream_off=so)
+    dst.check("AES-%d, an IV of all ones, %d windows per lane" % (bits, wpl))
+
+
+def test_in_place_full_windows_per_lane(hdfs, gpu_ctx, geom, cus, lanes, big):
+    """dst == src three bytes past a boundary, stream phase 13, one window over the last threshold: every
+    lane reads the lane_bytes / 16 windows it writes.  Encrypt, then decrypt back to the plaintext."""
+    full = geom["lane_bytes"] // 16
+    aes = hdfs.AesCtr(KEYS[256], IV)
+    big_b, big_t, big_addr = big
+    n = 16 * (_threshold(lanes, full) + 1) - 3 - 6
+    so = (1 << 50) + 13
+    dst = Dst(n + 64)
+    addr = dst.base + 19
+    _strided_info(hdfs, cus, full, addr, n)
+    dst.t[19:19 + n] = big_t[16:16 + n]
+    dst.expect(19, aes.xor(so, big_b[:n]))
+    gpu_ctx.aes_ctr_xor_strided(aes, addr, addr, n, stream_off=so)
+    dst.check("encrypt in place")
+    dst.expect(19, big_b[:n])
+    gpu_ctx.aes_ctr_xor_strided(aes, addr, addr, n, stream_off=so)
+    dst.check("decrypt in place")
 
 
 # ---- 3. key sizes and counter carries ---------------------------------------------------

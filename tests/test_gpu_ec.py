@@ -227,6 +227,104 @@ def test_striped_odd_cell(hdfs, gpu_ctx, data):
     dst.check("cells of 1000 bytes")
 
 
+def striped_src(buf, s_off, after=64):
+    """A block group's bytes in device memory, s_off bytes past a 16-byte boundary, between bytes of 0xA5
+    (a cell's end that is not masked shows: what follows the group is not zeros)."""
+    torch = _torch()
+    img = np.full(16 + s_off + buf.size + after, 0xA5, np.uint8)
+    img[16 + s_off:16 + s_off + buf.size] = buf
+    t = torch.from_numpy(img).cuda()
+    assert t.data_ptr() % 16 == 0
+    return t, t.data_ptr() + 16 + s_off
+
+
+def striped_case(hdfs, ctx, mx, buf, cell, s_off, p_offs, what):
+    """One hdfs_ec_encode_striped_dev call against host_striped_parity, whole output buffer compared."""
+    src_t, src = striped_src(buf, s_off)
+    par = host_striped_parity(hdfs, mx, buf, cell)
+    pitch = (par[0].size + 2 * cell + 63) // 16 * 16  # (room for a wrongly full last stripe to show)
+    dst = Dst(pitch * mx.n_out + 32)
+    outs = [dst.expect(16 + r * pitch + p_offs[r], par[r]) for r in range(mx.n_out)]
+    ctx.ec_encode_striped(mx, src, buf.size, cell, outs)
+    dst.check(what)
+
+
+@pytest.mark.parametrize("short", ["cell 1", "cell 2", "cell 0"])
+def test_striped_last_cell_tails(hdfs, gpu_ctx, data, short):
+    """RS(3,2), cells of 64 bytes, src 9 and the parities 2 and 13 bytes off a boundary: one full stripe,
+    then a stripe whose cell 1 has t bytes behind a full cell 0, whose cell 2 has t bytes behind two full
+    cells, and whose cell 0 itself has t bytes, for every t in 0 .. 33 -- every count of bytes the
+    short-cell mask keeps in a word, at every word of a window and into a third window.  All calls read
+    one source (bytes past a group's length are other data, not zeros) and write one buffer."""
+    k, m, cell = 3, 2, 64
+    mx = hdfs.EcMatrix.encode(k, m)
+    full_cells = {"cell 0": 0, "cell 1": 1, "cell 2": 2}[short]
+    tails = range(34)
+    top = k * cell + full_cells * cell + max(tails)
+    src_t, src = striped_src(data[100:100 + top + 40], 9, after=16)
+    row = (2 * cell + 13 + 31) // 16 * 16
+    dst = Dst(16 + len(tails) * m * row + 16)
+    for t in tails:
+        length = k * cell + full_cells * cell + t
+        par = host_striped_parity(hdfs, mx, data[100:100 + length], cell)
+        assert par[0].size == (cell + (cell if full_cells else t))
+        outs = [dst.expect(16 + (t * m + r) * row + (2, 13)[r], par[r]) for r in range(m)]
+        gpu_ctx.ec_encode_striped(mx, src, length, cell, outs)
+    dst.check("short %s" % short)
+
+
+@pytest.mark.parametrize("k,m", [(3, 2), (10, 4)])
+def test_striped_small_and_odd_cells(hdfs, gpu_ctx, data, k, m):
+    """Cells of 1, 2, 5, 15, 16, 17, 31 and 33 bytes (below 16: several stripes share one 16-byte window of
+    a parity block), 5 stripes + 2 cells + half a cell, every pointer off a boundary."""
+    mx = hdfs.EcMatrix.encode(k, m)
+    for cell in (1, 2, 5, 15, 16, 17, 31, 33):
+        length = 5 * k * cell + 2 * cell + cell // 2
+        striped_case(hdfs, gpu_ctx, mx, data[cell:cell + length], cell, 9, [2, 13, 7, 5][:m],
+                     "RS(%d,%d), cells of %d bytes" % (k, m, cell))
+
+
+@pytest.mark.parametrize("mode", ["aligned", "odd"])
+@pytest.mark.parametrize("scheme", ["rs-10-4", "xor-2-1", "16x4"])
+def test_striped_schemes(hdfs, gpu_ctx, data, scheme, mode):
+    """RS(10,4), XOR(2,1) and a 16 x 4 matrix of arbitrary coefficients over cells of 1024 + 16 bytes:
+    groups of 1 byte, one cell, one stripe - 1 / 0 / + 1 and 3 stripes + 2 cells + 77."""
+    mx = {"rs-10-4": lambda: hdfs.EcMatrix.encode(10, 4), "xor-2-1": lambda: hdfs.EcMatrix.encode(2, 1, hdfs.EC_XOR),
+          "16x4": lambda: rand_matrix(hdfs, 16, 4, 164)}[scheme]()
+    k, cell = mx.n_in, 1024 + 16
+    s_off, p_offs = (0, [0, 0, 0, 0]) if mode == "aligned" else (5, [3, 12, 7, 9])
+    for length in (1, cell, k * cell - 1, k * cell, k * cell + 1, 3 * k * cell + 2 * cell + 77):
+        striped_case(hdfs, gpu_ctx, mx, data[:length], cell, s_off, p_offs[:mx.n_out],
+                     "%s, group of %d bytes (%s)" % (scheme, length, mode))
+
+
+def test_striped_beyond_one_pass_of_the_grid(hdfs, gpu_ctx, geom):
+    """More wave units than waves in the launch, two per stripe: XOR(2,1) over cells of one wave unit with
+    parity 0 three bytes past a boundary (a stripe's second unit holds one window of 3 bytes), and
+    grid * waves_per_workgroup + 4 wave units -- the least even count that exceeds one pass by 3 or
+    more -- so some waves take a second unit and divide it by units_per_stripe == 2.  The last stripe's
+    cell 1 has 100 bytes.  Expected bytes: numpy's XOR of the cells."""
+    torch = _torch()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    mx = hdfs.EcMatrix.encode(2, 1, hdfs.EC_XOR)
+    assert mx.rows == [[1, 1]]
+    cell = geom["wave_bytes"]
+    per_cu = min(geom["max_workgroups_per_cu"], geom["lds_bytes_per_cu"] // (geom["lds_bytes_per_input"] * 2))
+    one_pass = per_cu * cus * geom["waves_per_workgroup"]
+    nstripes = (one_pass + 3 + 1) // 2
+    assert 2 * nstripes >= one_pass + 3
+    length = (nstripes - 1) * 2 * cell + cell + 100
+    buf = oracle.xorshift64_bytes(length, oracle.SEED + 4)
+    cells = np.concatenate([buf, np.zeros(cell - 100, np.uint8)]).reshape(nstripes, 2, cell)
+    want = (cells[:, 0] ^ cells[:, 1]).reshape(-1)
+    src_t, src = striped_src(buf, 6)
+    dst = Dst(want.size + 2 * cell + 64)
+    out = dst.expect(16 + 3, want)
+    assert out % 16 == 3
+    gpu_ctx.ec_encode_striped(mx, src, length, cell, [out])
+    dst.check("%d stripes of two wave units" % nstripes)
+
+
 # ---- 5. decode round trips -----------------------------------------------------------------------------
 @pytest.mark.parametrize("k,m,erased", [(6, 3, [0, 2, 5]), (10, 4, [1, 7, 10, 13])])
 def test_decode_round_trip(hdfs, gpu_ctx, data, k, m, erased):
