@@ -138,6 +138,14 @@ int crc32c_ctx_create(int device, crc32c_ctx **out);
 int crc32c_ctx_destroy(crc32c_ctx *ctx);
 /* Number of visible HIP devices (0 when there is no GPU). */
 int crc32c_device_count(void);
+/* Whether captured crc32c_plan_exec launches of the context's plans may
+ * overlap (section 3, "Captured into a HIP graph"): on != 0 by default, 0
+ * keeps every captured launch in plain stream order (per-launch durations in
+ * a profile, an A/B in one build).  The environment variable
+ * HDFS_CRC32C_CAPTURE_OVERLAP=0, read when a context is created, makes its
+ * default off.  Ends the current run of overlapping launches, if any.
+ * Returns the previous setting (0 / 1), or -EINVAL. */
+int crc32c_ctx_capture_overlap(crc32c_ctx *ctx, int on);
 
 /* ---------------------------------------------------------------------------
  * 3. Device-resident batches.
@@ -169,10 +177,33 @@ int crc32c_device_count(void);
  * is not reused while the context lives.
  * Payload and checksum buffers are device
  * pointers; execution is asynchronous on `stream` (a hipStream_t, NULL =
- * the default stream).  Exec launches of one plan are not ordered with each
- * other: independent batches may run on several streams at once, and two
- * streams let one launch start on the CUs the previous one has released
- * (config 2: 41.2 instead of 43.4 us per batch, tools/overlap_probe.py).
+ * the default stream).  Host-issued exec launches follow their stream's
+ * order and are not otherwise ordered with each other: independent batches
+ * may run on several streams at once, and two streams let one launch start
+ * on the CUs the previous one has released (config 2: 41.2 instead of 43.4
+ * us per batch, tools/overlap_probe.py).
+ * Captured into a HIP graph: a crc32c_plan_exec whose stream is being
+ * captured gets no edge from the previous captured crc32c_plan_exec of the
+ * context when the two provably touch nothing in common -- their checksum
+ * ranges [dev_out, dev_out + 4 nchecksums) are disjoint and neither's
+ * payload range (from the 16-byte boundary at or below dev_payload to the
+ * one after the last packet's end, the read-ahead rule below) overlaps the
+ * other's checksum range -- so on replay it starts on the CUs the previous
+ * launch releases, as on two streams.  The launches alternate over two
+ * chains of the graph (exec k follows exec k - 2), every chained exec is
+ * checked against the other chain, and when crc32c_plan_exec returns the
+ * stream's capture depends on every exec so far: whatever the stream gets
+ * next, the library's or the caller's, follows all of them, and a capture
+ * may end after any exec.  The stream's observable order is what it was.
+ * A launch keeps its stream-order edge when anything but these execs was
+ * put on the stream in between (a node, an event wait), when it is not
+ * independent, for plans without one payload base of known extent
+ * (CRC32C_DEVICE_ADDRESSES, crc32c_plan_create_buffers), for
+ * crc32c_plan_exec_blocks, verify launches and crc32c_chunks_dev, when the
+ * runtime's capture calls do not work, and with
+ * crc32c_ctx_capture_overlap(ctx, 0).  Plans of one context share this;
+ * nothing changes outside a capture.  As before, a plan must outlive the
+ * graphs that captured its launches.
  * Fast tiles: every full chunk of a packet with bpc in {512, 1024, 2048,
  * 4096, 8192}, at any alignment (off 16-byte alignment, loaded from the
  * aligned address below and shifted into place: config 2 five bytes off

@@ -80,6 +80,16 @@ int crc32c_debug_blocks_worker_cpu_ns(crc32c_blocks *q, uint64_t *ns);
  * none): tests see a destroyed plan's block come back from the pool. */
 uint64_t crc32c_debug_plan_block(const crc32c_plan *plan);
 
+/* Captured crc32c_plan_exec launches of the context so far (hdfs_crc32c.h
+ * section 3, "Captured into a HIP graph"): out[0] = execs captured, out[1] =
+ * those launched with no edge from the previous captured exec, out[2] = runs
+ * of overlapping execs started (a run starts at the first exec of a capture
+ * and wherever an exec has to keep its stream-order edge).  No GPU work. */
+int crc32c_ctx_capture_stats(crc32c_ctx *ctx, uint64_t out[3]);
+/* The same for the context of a multi-GPU handle's local device `local`
+ * (its shard launches never chain: they go on the plan's own exec streams). */
+int crc32c_debug_multi_capture_stats(crc32c_multi *m, int local, uint64_t out[3]);
+
 /* The production kernel build a launch runs: the instantiation
  * hdfs_crc32c_plan_kernel<threads, waves_per_simd, mode> (mode: the kernel's
  * template bits, csrc/plan_select.h), the units each tile is split into (4

@@ -230,6 +230,9 @@ def _bind(L):
         "crc32c_device_count": (i32, []),
         "crc32c_ctx_create": (i32, [i32, pp]),
         "crc32c_ctx_destroy": (i32, [vp]),
+        "crc32c_ctx_capture_overlap": (i32, [vp, i32]),
+        "crc32c_ctx_capture_stats": (i32, [vp, ctypes.POINTER(u64)]),
+        "crc32c_debug_multi_capture_stats": (i32, [vp, i32, ctypes.POINTER(u64)]),
         "crc32c_plan_create": (i32, [vp, vp, sz, u32, pp]),
         "crc32c_plan_exec": (i32, [vp, vp, vp, vp]),
         "crc32c_plan_destroy": (i32, [vp]),
@@ -774,6 +777,22 @@ class Context:
         except Exception:
             pass
 
+    def capture_overlap(self, on: bool) -> bool:
+        """crc32c_ctx_capture_overlap: whether captured Plan.exec launches that
+        touch nothing in common may overlap (the default); returns the
+        previous setting."""
+        prev = int(lib().crc32c_ctx_capture_overlap(self.handle, 1 if on else 0))
+        if prev < 0:
+            _check(prev, "crc32c_ctx_capture_overlap")
+        return bool(prev)
+
+    def capture_stats(self):
+        """crc32c_ctx_capture_stats: (execs captured, those with no edge from
+        the previous captured exec, runs started)."""
+        out = (ctypes.c_uint64 * 3)()
+        _check(lib().crc32c_ctx_capture_stats(self.handle, out), "crc32c_ctx_capture_stats")
+        return int(out[0]), int(out[1]), int(out[2])
+
     def plan(self, pkts, flags: int = 0) -> "Plan":
         return Plan(self, pkts, flags)
 
@@ -1139,6 +1158,12 @@ class Multi:
 
     def plan(self, pkts, group_packets: int = 64, flags: int = 0) -> "MultiPlan":
         return MultiPlan(self, pkts, group_packets, flags)
+
+    def capture_stats(self, local: int = 0):
+        """Context.capture_stats of local device ``local``'s context."""
+        out = (ctypes.c_uint64 * 3)()
+        _check(lib().crc32c_debug_multi_capture_stats(self.handle, local, out), "crc32c_debug_multi_capture_stats")
+        return int(out[0]), int(out[1]), int(out[2])
 
     def sync(self) -> None:
         _check(lib().crc32c_multi_sync(self.handle), "crc32c_multi_sync")

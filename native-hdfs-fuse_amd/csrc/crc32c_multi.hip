@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "hdfs_crc32c.h"
+#include "hdfs_crc32c_debug.h"
 #include "plan.h"
 #include "runtime_internal.h"
 
@@ -501,7 +502,7 @@ int exec_pipelined(crc32c_multi_plan *mp, const void *const *dev_shards, uint32_
         const bool in_place = !mp->d_local[i];
         if (in_place && same_root && P.kern_rec[1 - b]) HIP_TRY(hipStreamWaitEvent(E, P.kern[1 - b], 0));
         uint32_t *dst = in_place ? root_out : (b ? mp->d_local2[i] : mp->d_local[i]);
-        if (int rc = crc32c_plan_exec(mp->plans[i], dev_shards[i], dst, E)) return rc;
+        if (int rc = plan_exec(mp->plans[i], dev_shards[i], dst, E, false)) return rc;  // (its own forked stream: no chaining)
         HIP_TRY(hipEventRecord(P.kern[b], E));
         P.kern_rec[b] = true;
     }
@@ -599,6 +600,11 @@ int crc32c_multi_sync(crc32c_multi *m) {
         HIP_TRY(hipStreamSynchronize(m->streams[i]));
     }
     return 0;
+}
+
+int crc32c_debug_multi_capture_stats(crc32c_multi *m, int local, uint64_t out[3]) {
+    if (!m || local < 0 || size_t(local) >= m->ctxs.size()) return fail(-EINVAL, "multi == NULL or no such local device");
+    return crc32c_ctx_capture_stats(m->ctxs[size_t(local)], out);
 }
 
 int64_t crc32c_multi_layout(const crc32c_packet *pkts, size_t npkts, uint32_t group_packets, int nranks,
@@ -811,7 +817,7 @@ int crc32c_multi_plan_exec(crc32c_multi_plan *mp, const void *const *dev_shards,
     for (size_t i = 0; i < m->ctxs.size(); ++i) {
         if (!mp->local_nout[size_t(m->ranks[i])]) continue;
         uint32_t *dst = mp->d_local[i] ? mp->d_local[i] : root_out;
-        if (int rc = crc32c_plan_exec(mp->plans[i], dev_shards[i], dst, local_stream(m, i, streams))) return rc;
+        if (int rc = plan_exec(mp->plans[i], dev_shards[i], dst, local_stream(m, i, streams), false)) return rc;
     }
     // 2. one group of point-to-point transfers: every sender's group ranges
     //    from its local array, rank 0's receives straight into file order

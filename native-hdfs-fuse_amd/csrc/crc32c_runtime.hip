@@ -519,16 +519,7 @@ int alloc_slots(SchedSlots &s) {
 }
 
 // The CUs a launch is sized for.
-// (A/B knob HDFS_CRC32C_CU_CAP=n: launches size their grid for at most n
-// CUs, leaving the rest to kernels beside them -- an RCCL group
-// overlapping a pipelined multi-plan step; measured no gain)
-uint32_t launch_cus(const crc32c_ctx *ctx) {
-    static const int cap = [] {
-        const char *e = std::getenv("HDFS_CRC32C_CU_CAP");
-        return e ? std::atoi(e) : 0;
-    }();
-    return uint32_t(cap > 0 && cap < ctx->num_cu ? cap : ctx->num_cu);
-}
+uint32_t launch_cus(const crc32c_ctx *ctx) { return uint32_t(ctx->num_cu); }
 
 // Launches p on `stream`.  Verification launches use the sequence's slot
 // (left reset by the previous one); the caller keeps launches on `slots`
@@ -566,7 +557,161 @@ int order_plan_launch(crc32c_plan *plan, hipStream_t stream) {
     return 0;
 }
 
-int launch_plan(crc32c_plan *plan, const KParams &p, hipStream_t stream, hipEvent_t stop = nullptr) {
+// ---- Captured exec launches that may overlap (hdfs_crc32c.h section 3;
+// the rule and the bookkeeping: capture_chain.h).
+//
+// A stream being captured gives every node an edge from the one before it,
+// so a graph of K execs is one chain: each launch waits for the last
+// workgroup of the previous one, and the per-launch fixed costs (table
+// staging, the tail while the last CUs finish, the kernel boundary) are
+// paid end to end.  Where consecutive execs are independent those edges
+// order nothing: exec k of a run goes on chain k mod 2 -- after the run's
+// fork set and the chain's previous exec only -- and the stream's
+// dependency set is then put back to both chains' tails, so every later
+// node of the stream, the library's or anyone's, follows every exec, and a
+// capture may end after any exec with nothing left to join.  Done with the
+// capture's own calls (hipStreamGetCaptureInfo_v2,
+// hipStreamUpdateCaptureDependencies) on the caller's stream: no side
+// stream, no event.
+
+std::once_flag g_capture_probe_once;
+bool g_capture_calls_ok = false;
+
+// Whether this runtime's capture-info and dependency-update calls do what
+// capture_exec needs, tried once per process outside any caller's capture:
+// an empty capture of a private stream in thread-local mode, two empty
+// nodes set as its dependencies and read back, then one.  When they do not,
+// captured execs keep plain stream order for the whole process.
+void probe_capture_calls() {
+    RelaxedCapture relaxed;
+    hipStream_t s = nullptr;
+    hipGraph_t g = nullptr, cg = nullptr;
+    bool ok = false;
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess &&
+        hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        unsigned long long id = 0;
+        const hipGraphNode_t *d = nullptr;
+        size_t n = 0;
+        hipGraphNode_t a = nullptr, b = nullptr;
+        if (hipStreamGetCaptureInfo_v2(s, &st, &id, &cg, &d, &n) == hipSuccess &&
+            st == hipStreamCaptureStatusActive && cg && n == 0 &&
+            hipGraphAddEmptyNode(&a, cg, nullptr, 0) == hipSuccess &&
+            hipGraphAddEmptyNode(&b, cg, nullptr, 0) == hipSuccess) {
+            hipGraphNode_t set[2] = {a, b};
+            if (hipStreamUpdateCaptureDependencies(s, set, 2, hipStreamSetCaptureDependencies) == hipSuccess &&
+                hipStreamGetCaptureInfo_v2(s, &st, &id, nullptr, &d, &n) == hipSuccess && n == 2 &&
+                ((d[0] == a && d[1] == b) || (d[0] == b && d[1] == a)) &&
+                hipStreamUpdateCaptureDependencies(s, set, 1, hipStreamSetCaptureDependencies) == hipSuccess &&
+                hipStreamGetCaptureInfo_v2(s, &st, &id, nullptr, &d, &n) == hipSuccess && n == 1 && d[0] == a)
+                ok = true;
+        }
+        (void)hipStreamEndCapture(s, &g);
+    }
+    if (g) (void)hipGraphDestroy(g);
+    if (s) (void)hipStreamDestroy(s);
+    (void)hipGetLastError();
+    g_capture_calls_ok = ok;
+}
+
+// The capture id and dependency set of `s`; false: not being captured, or
+// the call failed (the error is cleared).
+bool capture_state(hipStream_t s, unsigned long long *id, std::vector<hipGraphNode_t> *deps) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    const hipGraphNode_t *d = nullptr;
+    size_t n = 0;
+    if (hipStreamGetCaptureInfo_v2(s, &st, id, nullptr, &d, &n) != hipSuccess ||
+        st != hipStreamCaptureStatusActive || (n && !d)) {
+        (void)hipGetLastError();
+        return false;
+    }
+    deps->assign(d, d + n);
+    return true;
+}
+
+bool set_capture_deps(hipStream_t s, std::vector<hipGraphNode_t> &deps) {
+    if (hipStreamUpdateCaptureDependencies(s, deps.data(), deps.size(), hipStreamSetCaptureDependencies) ==
+        hipSuccess)
+        return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+void add_node(std::vector<hipGraphNode_t> &v, hipGraphNode_t n) {
+    if (n && std::find(v.begin(), v.end(), n) == v.end()) v.push_back(n);
+}
+
+bool same_nodes(std::vector<hipGraphNode_t> a, std::vector<hipGraphNode_t> b) {
+    std::sort(a.begin(), a.end());
+    std::sort(b.begin(), b.end());
+    return a == b;
+}
+
+// One exec launch of `plan` on `stream`, which is being captured (caller
+// holds plan->mu).  er: the launch's ranges when it may chain (null: an
+// ineligible plan or caller; it ends the run and goes out in stream order).
+// A run also ends -- this exec then starts the next one, in plain stream
+// order -- when the stream's capture or dependency set is not what the
+// previous exec left (someone put a node or an event wait there), when the
+// exec is not independent of the other chain, when its chain's range list is
+// full, or when a capture call fails.
+int capture_exec(crc32c_plan *plan, const KParams &p, hipStream_t stream, const ExecRanges *er, uint32_t *grid) {
+    crc32c_ctx *ctx = plan->ctx;
+    CaptureChains &c = ctx->chains;
+    RelaxedCapture relaxed;
+    std::lock_guard<std::mutex> lock(c.mu);
+    ++c.captured;
+    unsigned long long id = 0;
+    std::vector<hipGraphNode_t> deps;
+    if (!er || !c.on || !g_capture_calls_ok || !capture_state(stream, &id, &deps)) {
+        c.active = false;
+        return launch(ctx, p, plan->sched, stream, nullptr, grid);
+    }
+    bool cont = c.active && c.id == id && c.stream == stream && same_nodes(deps, c.left) && c.run.admits(*er);
+    const uint32_t b = cont ? c.run.next_chain() : 0u;
+    std::vector<hipGraphNode_t> before;  // this exec's dependencies: the fork set and its chain's tail
+    if (cont) {
+        before = c.fork;
+        add_node(before, c.tail[b]);
+        cont = set_capture_deps(stream, before);
+    }
+    if (!cont) {
+        c.active = true;
+        c.id = id;
+        c.stream = stream;
+        c.fork = deps;
+        c.tail[0] = c.tail[1] = nullptr;
+        c.run.reset();
+        ++c.runs;
+    }
+    int rc = launch(ctx, p, plan->sched, stream, nullptr, grid);
+    std::vector<hipGraphNode_t> now;
+    const bool read = !rc && capture_state(stream, &id, &now);
+    const bool node = read && now.size() == 1;
+    const hipGraphNode_t made = node ? now[0] : nullptr;
+    if (cont) {
+        // the stream's frontier again holds every exec of the run: this
+        // node and the other chain's tail
+        if (!read) now = before;
+        add_node(now, c.tail[1u - b]);
+        if (!set_capture_deps(stream, now) || (!read && !rc)) {
+            c.active = false;
+            return rc ? rc : fail(-EIO, "a captured exec's node could not be joined to its stream");
+        }
+    }
+    if (!node) {
+        c.active = false;
+        return rc;
+    }
+    c.tail[b] = made;
+    c.left = now;
+    c.run.add(*er);
+    if (cont) ++c.unchained;
+    return 0;
+}
+
+int launch_plan(crc32c_plan *plan, const KParams &p, hipStream_t stream, hipEvent_t stop = nullptr,
+                bool exec_call = false, const ExecRanges *chain = nullptr) {
     std::lock_guard<std::mutex> lock(plan->mu);
     bool capturing = false;
     if (int rc = prepare_launch(plan, stream, &capturing)) return rc;
@@ -577,7 +722,11 @@ int launch_plan(crc32c_plan *plan, const KParams &p, hipStream_t stream, hipEven
         // wait: a previous verify still setting bits in it has finished)
     }
     uint32_t grid = 0;
-    const int rc = launch(plan->ctx, p, plan->sched, stream, stop, &grid);
+    // (a captured crc32c_plan_exec may go without an edge to the previous one)
+    const bool items = uint64_t(p.ntiles) + p.ngen + p.nseg + p.nconst != 0;
+    const int rc = capturing && exec_call && items && !stop
+                       ? capture_exec(plan, p, stream, chain, &grid)
+                       : launch(plan->ctx, p, plan->sched, stream, stop, &grid);
     // (its workgroups count themselves into the plan's completion counters;
     // a captured launch's plan block is never reused anyway)
     if (!rc && !capturing) plan->wgs_issued += grid;
@@ -971,6 +1120,8 @@ int crc32c_ctx_create(int device, crc32c_ctx **out) {
     HIP_TRY(preload_aes_kernels());
     HIP_TRY(preload_ec_kernels());
     c->host_pool.pinned = true;
+    std::call_once(g_capture_probe_once, probe_capture_calls);
+    if (const char *e = std::getenv("HDFS_CRC32C_CAPTURE_OVERLAP")) c->chains.on = std::atoi(e) != 0;
     HIP_TRY(hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking));
     for (int ty = 0; ty < 2; ++ty) {
         const uint32_t poly = ty ? kPolyIeee : kPoly;
@@ -1087,7 +1238,22 @@ int crc32c_plan_create(crc32c_ctx *ctx, const crc32c_packet *pkts, size_t npkts,
     if (rc) return fail(rc, "invalid packet batch");
     uint64_t base = 0;
     if (absolute) rebase_plan(&hp, &base);  // offsets from the lowest address (16-byte phase kept)
-    return make_plan(ctx, hp, flags, absolute, base, out);
+    rc = make_plan(ctx, hp, flags, absolute, base, out);
+    if (!rc && !absolute) {
+        // the bytes a launch may read from its payload base (0 on overflow: not known)
+        uint64_t extent = 0;
+        for (size_t i = 0; i < npkts; ++i) {
+            if (!pkts[i].len) continue;
+            const uint64_t end = pkts[i].payload_off + pkts[i].len;
+            if (end < pkts[i].payload_off) {
+                extent = 0;
+                break;
+            }
+            extent = std::max(extent, end);
+        }
+        (*out)->payload_extent = extent;
+    }
+    return rc;
 }
 
 int crc32c_plan_create_buffers(crc32c_ctx *ctx, const crc32c_buffer *buffers, uint32_t n_buffers,
@@ -1119,17 +1285,53 @@ static bool plan_reads_payload(const crc32c_plan *plan) {
 }
 
 int crc32c_plan_exec(crc32c_plan *plan, const void *dev_payload, uint32_t *dev_out, void *stream) {
-    if (!plan) return fail(-EINVAL, "plan == NULL");
-    if (plan->nchecksums == 0) return 0;
-    if (int rc = plan_payload(plan, &dev_payload)) return rc;
-    if ((!dev_payload && plan_reads_payload(plan)) || !dev_out) return fail(-EINVAL, "payload/out == NULL");
-    DeviceGuard guard(plan->ctx->device);
-    return launch_plan(plan, plan_params(plan, dev_payload, dev_out), static_cast<hipStream_t>(stream));
+    return plan_exec(plan, dev_payload, dev_out, static_cast<hipStream_t>(stream), true);
+}
+
+int crc32c_ctx_capture_overlap(crc32c_ctx *ctx, int on) {
+    if (!ctx) return fail(-EINVAL, "ctx == NULL");
+    std::lock_guard<std::mutex> lock(ctx->chains.mu);
+    const int prev = ctx->chains.on ? 1 : 0;
+    ctx->chains.on = on != 0;
+    ctx->chains.active = false;
+    return prev;
+}
+
+int crc32c_ctx_capture_stats(crc32c_ctx *ctx, uint64_t out[3]) {
+    if (!ctx || !out) return fail(-EINVAL, "ctx/out == NULL");
+    std::lock_guard<std::mutex> lock(ctx->chains.mu);
+    out[0] = ctx->chains.captured;
+    out[1] = ctx->chains.unchained;
+    out[2] = ctx->chains.runs;
+    return 0;
 }
 
 }  // extern "C"
 
 namespace hdfs_crc {
+
+int plan_exec(crc32c_plan *plan, const void *dev_payload, uint32_t *dev_out, hipStream_t stream, bool chain) {
+    if (!plan) return fail(-EINVAL, "plan == NULL");
+    if (plan->nchecksums == 0) return 0;
+    if (int rc = plan_payload(plan, &dev_payload)) return rc;
+    if ((!dev_payload && plan_reads_payload(plan)) || !dev_out) return fail(-EINVAL, "payload/out == NULL");
+    DeviceGuard guard(plan->ctx->device);
+    // The ranges of a launch that may chain when captured: a plan of one
+    // payload base and a known extent.  Read: from the 16-byte boundary at
+    // or below the base to the one after the extent's last byte (the
+    // header's read-ahead rule; a base off alignment is loaded from the
+    // aligned address below).  Written: the plan's checksums.
+    ExecRanges er;
+    const bool eligible = chain && !plan->absolute && (plan->payload_extent || !plan_reads_payload(plan));
+    if (eligible) {
+        const uint64_t base = uint64_t(reinterpret_cast<uintptr_t>(dev_payload));
+        const uint64_t lo = base & ~uint64_t(15);
+        if (plan_reads_payload(plan)) er.payload = byte_range(lo, round_up_16(base - lo + plan->payload_extent));
+        er.out = byte_range(uint64_t(reinterpret_cast<uintptr_t>(dev_out)), 4 * plan->nchecksums);
+    }
+    return launch_plan(plan, plan_params(plan, dev_payload, dev_out), stream, nullptr, chain,
+                       eligible ? &er : nullptr);
+}
 
 int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs, size_t nblocks,
                 hipStream_t s, hipEvent_t stop) {
@@ -1402,7 +1604,7 @@ int crc32c_chunks_dev(crc32c_ctx *ctx, const crc32c_packet *pkts, size_t npkts, 
     crc32c_plan *plan = nullptr;
     int rc = crc32c_plan_create(ctx, pkts, npkts, flags, &plan);
     if (rc) return rc;
-    rc = crc32c_plan_exec(plan, dev_payload, dev_out, stream);
+    rc = plan_exec(plan, dev_payload, dev_out, static_cast<hipStream_t>(stream), false);
     if (!rc) {
         DeviceGuard guard(ctx->device);
         hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(stream));

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "capture_chain.h"
 #include "errors.h"
 #include "hdfs_crc32c.h"
 #include "kernel_abi.h"
@@ -137,6 +138,24 @@ struct RelaxedCapture {
     ~RelaxedCapture() { (void)hipThreadExchangeStreamCaptureMode(&mode); }
 };
 
+// Captured exec launches that may overlap (crc32c_runtime.hip capture_exec;
+// the rule and the bookkeeping: capture_chain.h).  One run at a time per
+// context: the capture and stream it belongs to, the stream's dependency set
+// as the last exec left it (anything else there since -- a foreign node, an
+// event wait -- ends the run), the fork set every exec of the run follows,
+// and the last exec of each chain.
+struct CaptureChains {
+    std::mutex mu;
+    bool on = true;  // crc32c_ctx_capture_overlap / HDFS_CRC32C_CAPTURE_OVERLAP
+    uint64_t captured = 0, unchained = 0, runs = 0;  // crc32c_ctx_capture_stats
+    bool active = false;
+    unsigned long long id = 0;
+    hipStream_t stream = nullptr;
+    std::vector<hipGraphNode_t> left, fork;
+    hipGraphNode_t tail[2] = {nullptr, nullptr};
+    ChainRun run;
+};
+
 }  // namespace hdfs_crc
 
 struct crc32c_ctx {
@@ -170,6 +189,7 @@ struct crc32c_ctx {
     std::vector<std::pair<uint8_t *, size_t>> held;
     hipStream_t upload_stream = nullptr;
     std::vector<hipEvent_t> spare_events;
+    hdfs_crc::CaptureChains chains;
 };
 
 struct crc32c_plan {
@@ -199,6 +219,10 @@ struct crc32c_plan {
     bool unaccounted = false;
     hdfs_crc::DevicePlan dp;
     uint64_t nchecksums = 0, payload_bytes = 0;
+    // Packet plans on a caller's payload base: the bytes a launch may read
+    // from it, max over packets of payload_off + len (0: not known --
+    // absolute plans).
+    uint64_t payload_extent = 0;
     uint32_t flags = 0;
     // The composite shape of the plan's chunks (plan.h HostPlan::comp_bpc;
     // 0: the checksums do not combine with two constants).
@@ -225,6 +249,10 @@ int prepare_launch(crc32c_plan *plan, hipStream_t stream, bool *capturing = null
 // `stream` (idle, about to be destroyed by the library itself: a block
 // queue's) no longer needs an event at the plan's release.
 void plan_forget_stream(crc32c_plan *plan, hipStream_t stream);
+// crc32c_plan_exec; chain: a captured launch may go without an edge to the
+// previous captured exec (capture_exec); false: plain stream order, the
+// library's own forked exec streams (crc32c_multi.hip).
+int plan_exec(crc32c_plan *plan, const void *dev_payload, uint32_t *dev_out, hipStream_t stream, bool chain);
 // crc32c_plan_exec_blocks; `stop` (optional) is completed by the last launch.
 int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs, size_t nblocks,
                 hipStream_t stream, hipEvent_t stop);

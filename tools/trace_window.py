@@ -8,7 +8,12 @@ captured launches -- the `--steps` minus a host-issued lead of `--lead`
 power-settle launches (the line's `settle_launches`), then `--warmup`
 warm-up launches, then the `--steps` timed ones, of which the bench times
 the kernel over those after the lead.  Writes the window's average / median / min / max (ns) so it can be
-compared with bench.py's own HIP-event average for the same run.
+compared with bench.py's own HIP-event average for the same run, the
+start-to-start time per launch, and -- for graphs whose captured execs
+overlap (the default since round 8; HDFS_CRC32C_CAPTURE_OVERLAP=0 turns it
+off) -- how many consecutive launches overlap and the first-start-to-last-end
+time per launch, which then compare with the bench's figure instead of the
+durations.
 
     python tools/trace_window.py gpurun_out/prof/run_kernel_trace.csv \
         --kernel "hdfs_crc32c_plan_kernel<768, 3, 3>" [--warmup 500 --steps 2000] [--out f.json]
@@ -41,7 +46,18 @@ def main():
     nwin = args.steps - args.lead
     win = dur[first:first + nwin]
     starts = [int(r["Start_Timestamp"]) for r in rows[first:first + nwin]]
+    ends = [int(r["End_Timestamp"]) for r in rows[first:first + nwin]]
+    # consecutive launches whose [start, end) overlap (captured execs without
+    # an edge between them), and by how much on average
+    lap = [ends[i] - starts[i + 1] for i in range(len(starts) - 1) if starts[i + 1] < ends[i]]
     res = {
+        "window_overlapping_pairs": len(lap), "window_pairs": max(len(starts) - 1, 0),
+        "window_overlap_avg_ns": round(statistics.mean(lap), 1) if lap else 0.0,
+        # first start to last end over the launches: what compares with the
+        # bench's event time when launches overlap (a launch's duration then
+        # includes the time its workgroups wait for CUs, and the last start
+        # comes early)
+        "window_wall_per_launch_ns": round((max(ends) - starts[0]) / max(len(starts), 1), 1),
         "kernel": args.kernel, "launches_in_trace": len(dur), "window": [first, first + len(win)],
         "window_avg_ns": round(statistics.mean(win), 1), "window_median_ns": statistics.median(win),
         "window_min_ns": min(win), "window_max_ns": max(win),
