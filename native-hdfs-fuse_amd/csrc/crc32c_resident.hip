@@ -85,7 +85,7 @@ int ensure_running(ResidentEngine *r) {
     p.table_s4 = kp.table_s4;
     p.flags = kp.flags;
     const DevicePlan &dp = r->plan->dp;
-    p.def = Shape{kp.tiles, kp.gen, dp.ntiles, dp.ngen, (!dp.ngen && !dp.misaligned && !dp.general) ? 1u : 0u};
+    p.def = Shape{kp.tiles, kp.gen, dp.ntiles, dp.ngen, dp.traits.simple ? 1u : 0u};
     for (int i = 0; i < 5; ++i) p.c_lg[i] = kp.c_lg[i];
     for (int i = 0; i < 4; ++i) p.c_small[i] = kp.c_small[i];
     p.first = col;
@@ -111,7 +111,8 @@ int ensure_running(ResidentEngine *r) {
 // queue's.
 int shape_ok(const ResidentEngine *r, const crc32c_plan *plan) {
     const DevicePlan &dp = plan->dp;
-    if (dp.nseg || dp.nconst || dp.half || dp.padtiles || !dp.gen_pow2 || plan->absolute)
+    if (dp.nseg || dp.nconst || (dp.traits.general & (kGeneralHalf | kGeneralPadded)) || !dp.traits.gen_pow2 ||
+        plan->absolute)
         return fail(-EINVAL, "the resident kernel runs blocks of bytesPerChecksum 512 << k (power-of-two tiles, "
                              "packet tails and trimmed first packets), payload offsets from the block start: no half, "
                              "padded or general tiles of other chunk lengths, no buffer lists");
@@ -192,7 +193,7 @@ int resident_create(crc32c_plan *plan, uint32_t idle_us, ResidentLaunch launch, 
     r->idle_ticks = uint64_t(idle_us ? idle_us : 2000) * kTicksPerUs;
     r->launch = launch;
     r->launch_general = launch_general;
-    r->plan_simple = !plan->dp.ngen && !plan->dp.misaligned && !plan->dp.general;
+    r->plan_simple = plan->dp.traits.simple;
     DeviceGuard guard(r->device);
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&r->h), sizeof(HostRing), hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(static_cast<void *>(r->h), 0, sizeof(HostRing));

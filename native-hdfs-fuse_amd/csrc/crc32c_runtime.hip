@@ -89,70 +89,6 @@ static KParams base_params(const crc32c_ctx *ctx, const void *payload, uint32_t 
     return p;
 }
 
-// General tiles or padded power-of-two tiles: both run in the builds with
-// the general-tile code (kGeneralItems).
-static bool has_general(const HostPlan &hp) {
-    for (const FastTile &t : hp.tiles)
-        if ((t.meta & (kGeneralTile | kHalfTile)) || tile_pad_bits(t.meta)) return true;
-    return false;
-}
-
-// Some work item shifts block results by Z^(512 s): power-of-two tiles of
-// bpc > 512 (lg > 0), general tiles and the general / spanning items.  A
-// batch of bpc-512 tiles only (configs 2, 3, 4) stages the image without
-// its Z section: 80 of 88 KiB (split image), 20 of 28 KiB (compact).
-static bool needs_z(const HostPlan &hp) {
-    if (!hp.gen.empty() || !hp.seg.empty()) return true;
-    for (const FastTile &t : hp.tiles)
-        if ((t.meta & kGeneralTile) || ((t.meta >> 8) & 0xffu)) return true;
-    return false;
-}
-
-// Some general tile's full chunks are padded (bpc not a multiple of 512), or
-// some tile is a padded power-of-two one.  Such batches run the general build
-// with both paths even without shifted tiles: the general-tiles-only build,
-// which helps unpadded general tiles (412-byte tails: 48.2 -> 46.2 us), was
-// measured slower for padded ones (bpc 1000: 62.8 -> 64.3 us, same box, 3
-// rounds; padded power-of-two tiles of bpc 2000, kbench: 48.46 against
-// 46.77 us, round 5).
-static bool has_padded_general(const HostPlan &hp) {
-    static const bool off = [] {  // (A/B: HDFS_CRC32C_PADDED_FULL=0 sends them to the general-tiles-only build)
-        const char *e = std::getenv("HDFS_CRC32C_PADDED_FULL");
-        return e && e[0] == '0';
-    }();
-    if (off) return false;
-    for (const FastTile &t : hp.tiles)
-        if (tile_pad_bits(t.meta) && !(t.meta & kHalfTile)) return true;  // (general or padded power-of-two tiles)
-    return false;
-}
-
-static bool has_padded_tiles(const HostPlan &hp) {
-    for (const FastTile &t : hp.tiles)
-        if (!(t.meta & (kGeneralTile | kHalfTile)) && tile_pad_bits(t.meta)) return true;
-    return false;
-}
-
-static bool has_half(const HostPlan &hp) {
-    for (const FastTile &t : hp.tiles)
-        if ((t.meta & (kGeneralTile | kHalfTile)) == kHalfTile) return true;
-    return false;
-}
-
-// Some power-of-two tile starts off 16-byte alignment (the general build's
-// shifted loads read it from the aligned address below).
-static bool has_misaligned(const HostPlan &hp) {
-    for (const FastTile &t : hp.tiles)
-        if (!(t.meta & (kGeneralTile | kHalfTile)) && !tile_pad_bits(t.meta) && (t.src & 15u)) return true;
-    return false;
-}
-
-// KParams::general of a launch over hp's items on a 16-byte aligned payload.
-static uint32_t general_bits(const HostPlan &hp) {
-    return (has_general(hp) ? kGeneralItems : 0u) |
-           ((has_misaligned(hp) || (has_padded_general(hp) && !has_half(hp))) ? kGeneralShift : 0u) |
-           (has_half(hp) ? kGeneralHalf : 0u) | (has_padded_tiles(hp) ? kGeneralPadded : 0u);
-}
-
 KParams plan_params(const crc32c_plan *plan, const void *payload, uint32_t *out) {
     KParams p = base_params(plan->ctx, payload, out, plan->flags);
     const DevicePlan &dp = plan->dp;
@@ -165,13 +101,8 @@ KParams plan_params(const crc32c_plan *plan, const void *payload, uint32_t *out)
     p.ngen = dp.ngen;
     p.nseg = dp.nseg;
     p.nconst = dp.nconst;
-    // the general builds: general tiles (bit 0), shifted loads of tiles off 16-byte alignment (bit 1)
-    p.general = (dp.general ? kGeneralItems : 0u) |
-                ((dp.misaligned || (dp.padded && !dp.half) || (reinterpret_cast<uintptr_t>(p.payload) & 15u))
-                     ? kGeneralShift
-                     : 0u) |
-                (dp.half ? kGeneralHalf : 0u) | (dp.padtiles ? kGeneralPadded : 0u);
-    p.skip_z = dp.needs_z ? 0u : 1u;
+    p.general = launch_general(dp.traits, (reinterpret_cast<uintptr_t>(p.payload) & 15u) != 0);
+    p.skip_z = dp.traits.needs_z ? 0u : 1u;
     p.done_ctr = plan->counted ? reinterpret_cast<unsigned long long *>(dp.d + kDoneCtrOff) : nullptr;
     return p;
 }
@@ -200,9 +131,6 @@ void drop_block(BlockPool &pool, uint8_t *p) {
         }
 }
 
-// Moves every release whose events have all completed back into the pools
-// (non-blocking queries), then trims the free lists to kFreeBlocksMax.
-// Caller holds ctx->pool_mu.
 // The launches of a release's plan have all completed: its completion
 // counters, read back into its pinned staging block on the upload stream by
 // the previous call (a read is issued here when none is in flight), sum to
@@ -241,6 +169,9 @@ bool launches_done(crc32c_ctx *ctx, Release &r) {
     return false;
 }
 
+// Moves every release whose events have all completed back into the pools
+// (non-blocking queries), then trims the free lists to kFreeBlocksMax.
+// Caller holds ctx->pool_mu.
 void reap_releases(crc32c_ctx *ctx) {
     for (size_t i = 0; i < ctx->releases.size();) {
         Release &r = ctx->releases[i];
@@ -312,18 +243,7 @@ int upload_plan(crc32c_ctx *ctx, const HostPlan &hp, DevicePlan *dp) {
     dp->ngen = uint32_t(hp.gen.size());
     dp->nseg = uint32_t(hp.seg.size());
     dp->nconst = uint32_t(hp.consts.size());
-    dp->general = has_general(hp);
-    dp->misaligned = has_misaligned(hp);
-    dp->padded = has_padded_general(hp);
-    dp->half = has_half(hp);
-    dp->padtiles = has_padded_tiles(hp);
-    dp->needs_z = needs_z(hp);
-    dp->gen_pow2 = true;
-    for (const FastTile &t : hp.tiles)
-        if ((t.meta & (kGeneralTile | kHalfTile)) == kGeneralTile) {
-            const uint32_t k = (t.meta >> 8) & 31u, pad = (t.meta >> 18) & 511u;  // (crc32c_general.h gshape)
-            if (pad || !k || (k & (k - 1u))) dp->gen_pow2 = false;
-        }
+    dp->traits = plan_traits(hp);
     dp->slots_off = 0;  // the verify slot first, the completion counters, then the work items
     static_assert(kSlotWords * sizeof(uint32_t) <= kDoneCtrOff, "the verify slot precedes the counters");
     dp->tiles_off = kPlanHeadBytes;
@@ -349,7 +269,7 @@ int upload_plan(crc32c_ctx *ctx, const HostPlan &hp, DevicePlan *dp) {
     rs.gen = reinterpret_cast<const GenItem *>(dp->d + dp->gen_off);
     rs.ntiles = dp->ntiles;
     rs.ngen = dp->ngen;
-    rs.simple = (!dp->ngen && !dp->misaligned && !dp->general) ? 1u : 0u;
+    rs.simple = dp->traits.simple ? 1u : 0u;
     std::memcpy(img + kResShapeOff, &rs, sizeof rs);
     std::memcpy(img + dp->tiles_off, hp.tiles.data(), hp.tiles.size() * sizeof(FastTile));
     std::memcpy(img + dp->gen_off, hp.gen.data(), hp.gen.size() * sizeof(GenItem));
@@ -518,9 +438,6 @@ int alloc_slots(SchedSlots &s) {
     return 0;
 }
 
-// The CUs a launch is sized for.
-uint32_t launch_cus(const crc32c_ctx *ctx) { return uint32_t(ctx->num_cu); }
-
 // Launches p on `stream`.  Verification launches use the sequence's slot
 // (left reset by the previous one); the caller keeps launches on `slots`
 // in GPU order.  *grid: the workgroups launched (0: none).
@@ -538,7 +455,7 @@ int launch(const crc32c_ctx *ctx, KParams p, SchedSlots &slots, hipStream_t stre
         if (rc) return rc;
         p.sched = slots.d;
     }
-    HIP_TRY(launch_plan_kernel(p, launch_cus(ctx), stream, stop, grid));
+    HIP_TRY(launch_plan_kernel(p, uint32_t(ctx->num_cu), stream, stop, grid));
     return 0;
 }
 
@@ -738,13 +655,6 @@ constexpr uint32_t kKnownFlags =
 
 int check_flags(uint32_t flags) {
     if (flags & ~kKnownFlags) return fail(-EINVAL, "unknown flags 0x%x", flags & ~kKnownFlags);
-    return 0;
-}
-
-int check_packets(const crc32c_packet *pkts, size_t npkts) {
-    if (npkts && !pkts) return fail(-EINVAL, "packets == NULL");
-    for (size_t i = 0; i < npkts; ++i)
-        if (pkts[i].len && pkts[i].bpc == 0) return fail(-EINVAL, "packet %zu: bytesPerChecksum == 0", i);
     return 0;
 }
 
@@ -1000,8 +910,9 @@ int batch_host_locked(crc32c_ctx *ctx, const uint8_t *payload, const crc32c_pack
         p.ngen = uint32_t(plan.gen.size());
         // (the staged slices keep every packet's 16-byte phase: tiles off
         // alignment take the general build's shifted loads, as in plans)
-        p.general = general_bits(plan);
-        p.skip_z = needs_z(plan) ? 0u : 1u;
+        const PlanTraits traits = plan_traits(plan);
+        p.general = launch_general(traits, false);
+        p.skip_z = traits.needs_z ? 0u : 1u;
         rc = launch(ctx, p, s.sched, s.stream);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(s.done, s.stream));
@@ -1333,6 +1244,31 @@ int plan_exec(crc32c_plan *plan, const void *dev_payload, uint32_t *dev_out, hip
                        eligible ? &er : nullptr);
 }
 
+// Kernel parameters of one multi-block launch of a tiles-only plan over
+// blocks i .. j - 1 (at most kMaxLaunchBlocks): payload deltas from the
+// lowest 16-byte aligned address among them, block k's output at
+// out + out_delta(k); a block off 16-byte alignment takes the shifted loads.
+template <typename OutDelta>
+static KParams blocks_params(const crc32c_plan *plan, const void *const *dev_payloads, size_t i, size_t j,
+                             uint32_t *out, OutDelta out_delta) {
+    uintptr_t plo = UINTPTR_MAX;
+    for (size_t k = i; k < j; ++k) plo = std::min(plo, uintptr_t(dev_payloads[k]) & ~uintptr_t(15));
+    KParams p = plan_params(plan, reinterpret_cast<const void *>(plo), out);
+    p.nblocks = uint32_t(j - i);
+    p.block_tiles = plan->dp.ntiles;
+    p.ntiles = uint32_t(uint64_t(j - i) * plan->dp.ntiles);
+    bool misaligned = false;
+    for (size_t k = i; k < j; ++k) {
+        BlockRef &b = p.blocks[k - i];
+        b.payload_delta = uint64_t(uintptr_t(dev_payloads[k]) - plo);
+        b.out_delta = out_delta(k);
+        b.reserved = 0;
+        misaligned = misaligned || (b.payload_delta & 15u);
+    }
+    p.general = launch_general(plan->dp.traits, misaligned);
+    return p;
+}
+
 int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs, size_t nblocks,
                 hipStream_t s, hipEvent_t stop) {
     if (!plan) return fail(-EINVAL, "plan == NULL");
@@ -1372,17 +1308,9 @@ int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *co
                 break;
             plo = nplo, phi = nphi, olo = nolo, ohi = nohi;
         }
-        KParams p = plan_params(plan, reinterpret_cast<const void *>(plo), reinterpret_cast<uint32_t *>(olo));
-        p.nblocks = uint32_t(j - i);
-        p.block_tiles = dp.ntiles;
-        p.ntiles = uint32_t(uint64_t(j - i) * dp.ntiles);
-        for (size_t k = i; k < j; ++k) {
-            BlockRef &b = p.blocks[k - i];
-            b.payload_delta = uint64_t(uintptr_t(dev_payloads[k]) - plo);
-            b.out_delta = uint32_t((uintptr_t(dev_outs[k]) - olo) / 4);
-            b.reserved = 0;
-            if (b.payload_delta & 15u) p.general |= kGeneralShift;  // (shifted loads for blocks off 16-byte alignment)
-        }
+        const KParams p = blocks_params(plan, dev_payloads, i, j, reinterpret_cast<uint32_t *>(olo), [&](size_t k) {
+            return uint32_t((uintptr_t(dev_outs[k]) - olo) / 4);
+        });
         if (int rc = launch_plan(plan, p, s, j == nblocks ? stop : nullptr)) return rc;
         i = j;
     }
@@ -1448,19 +1376,8 @@ int crc32c_plan_verify_blocks(crc32c_plan *plan, const void *const *dev_payloads
     uint32_t *results = bitmap + verify_blocks_bitmap_words(plan, nblocks);
     for (size_t i = 0, g = 0; i < nblocks; i += kMaxLaunchBlocks, ++g) {
         const size_t j = std::min<size_t>(nblocks, i + kMaxLaunchBlocks);
-        uintptr_t plo = UINTPTR_MAX;
-        for (size_t k = i; k < j; ++k) plo = std::min(plo, uintptr_t(dev_payloads[k]) & ~uintptr_t(15));
-        KParams p = plan_params(plan, reinterpret_cast<const void *>(plo), nullptr);
-        p.nblocks = uint32_t(j - i);
-        p.block_tiles = dp.ntiles;
-        p.ntiles = uint32_t(uint64_t(j - i) * dp.ntiles);
-        for (size_t k = i; k < j; ++k) {
-            BlockRef &b = p.blocks[k - i];
-            b.payload_delta = uint64_t(uintptr_t(dev_payloads[k]) - plo);
-            b.out_delta = uint32_t((k - i) * n);  // expected values and bitmap bits of the launch's block k - i
-            b.reserved = 0;
-            if (b.payload_delta & 15u) p.general |= kGeneralShift;  // (shifted loads for blocks off 16-byte alignment)
-        }
+        // (out_delta: expected values and bitmap bits of the launch's block k - i)
+        KParams p = blocks_params(plan, dev_payloads, i, j, nullptr, [&](size_t k) { return uint32_t((k - i) * n); });
         // 32 n bits are whole words: launch g's bitmap starts at word g n and
         // its own clear (verify_init) covers exactly its words
         p.expect = dev_expected + uint64_t(i) * n;
@@ -1584,18 +1501,8 @@ int crc32c_debug_plan_launch_info(const crc32c_plan *plan, const void *dev_paylo
     out->nconst = p.nconst;
     out->general = p.general;
     out->skip_z = p.skip_z;
-    out->num_cu = launch_cus(plan->ctx);
+    out->num_cu = uint32_t(plan->ctx->num_cu);
     put_build(select_plan_build(p.ntiles, p.ngen, p.nseg, p.nconst, p.general, verify != 0, out->num_cu), &out->build);
-    return 0;
-}
-
-int crc32c_debug_packets_flags(const crc32c_packet *pkts, size_t npkts, int absolute, uint32_t *general_bits_out,
-                               int *needs_z_out) {
-    if (int rc = check_packets(pkts, npkts)) return rc;
-    HostPlan hp;
-    if (int rc = build_plan(pkts, npkts, &hp, absolute != 0)) return fail(rc, "invalid packet in batch");
-    if (general_bits_out) *general_bits_out = general_bits(hp);
-    if (needs_z_out) *needs_z_out = needs_z(hp) ? 1 : 0;
     return 0;
 }
 

@@ -8,7 +8,9 @@
 #include <cstring>
 
 #include "crc_math.h"
+#include "errors.h"
 #include "hdfs_crc32c_debug.h"
+#include "plan_select.h"
 
 namespace hdfs_crc {
 
@@ -474,7 +476,77 @@ void rebase_plan(HostPlan *plan, uint64_t *base) {
     *base = lo;
 }
 
+// Some general tile's full chunks are padded (bpc not a multiple of 512), or
+// some tile is a padded power-of-two one.  Such batches run the general build
+// with both paths even without shifted tiles: the general-tiles-only build,
+// which helps unpadded general tiles (412-byte tails: 48.2 -> 46.2 us), was
+// measured slower for padded ones (bpc 1000: 62.8 -> 64.3 us, same box, 3
+// rounds; padded power-of-two tiles of bpc 2000, kbench: 48.46 against
+// 46.77 us, round 5).
+static bool padded_full_on() {
+    static const bool off = [] {  // (A/B: HDFS_CRC32C_PADDED_FULL=0 sends them to the general-tiles-only build)
+        const char *e = std::getenv("HDFS_CRC32C_PADDED_FULL");
+        return e && e[0] == '0';
+    }();
+    return !off;
+}
+
+PlanTraits plan_traits(const HostPlan &hp) {
+    PlanTraits t;
+    t.needs_z = !hp.gen.empty() || !hp.seg.empty();
+    // misaligned: some power-of-two tile starts off 16-byte alignment (the general build's shifted loads read
+    // it from the aligned address below); padded: some general or power-of-two tile's chunks are padded
+    bool misaligned = false, padded = false;
+    for (const FastTile &ft : hp.tiles) {
+        const uint32_t pad = tile_pad_bits(ft.meta);
+        if ((ft.meta >> 8) & 0xffu) t.needs_z = true;  // (lg, M or k: blocks to shift over)
+        switch (ft.meta & (kGeneralTile | kHalfTile)) {
+        case 0:  // (padded power-of-two tiles run in the builds with the general-tile code)
+            if (pad) t.general |= kGeneralItems | kGeneralPadded;
+            padded = padded || pad;
+            misaligned = misaligned || (!pad && (ft.src & 15u));
+            break;
+        case kHalfTile:
+            t.general |= kGeneralItems | kGeneralHalf;
+            break;
+        case kGeneralTile:  // (k blocks per chunk: crc32c_general.h gshape)
+            if (const uint32_t k = (ft.meta >> 8) & 31u; pad || !k || (k & (k - 1u))) t.gen_pow2 = false;
+            padded = padded || pad;
+            [[fallthrough]];
+        default:  // (both bits: the builders above never set both; a general tile whose fields are not read)
+            t.general |= kGeneralItems;
+            t.needs_z = true;
+        }
+    }
+    if (misaligned || (padded && !(t.general & kGeneralHalf) && padded_full_on())) t.general |= kGeneralShift;
+    t.simple = hp.gen.empty() && !misaligned && !(t.general & kGeneralItems);
+    return t;
+}
+
+uint32_t launch_general(const PlanTraits &t, bool base_or_block_misaligned) {
+    return t.general | (base_or_block_misaligned ? kGeneralShift : 0u);
+}
+
+int check_packets(const crc32c_packet *pkts, size_t npkts) {
+    if (npkts && !pkts) return fail(-EINVAL, "packets == NULL");
+    for (size_t i = 0; i < npkts; ++i)
+        if (pkts[i].len && pkts[i].bpc == 0) return fail(-EINVAL, "packet %zu: bytesPerChecksum == 0", i);
+    return 0;
+}
+
 }  // namespace hdfs_crc
+
+extern "C" int crc32c_debug_packets_flags(const crc32c_packet *pkts, size_t npkts, int absolute,
+                                          uint32_t *general_bits_out, int *needs_z_out) {
+    if (int rc = hdfs_crc::check_packets(pkts, npkts)) return rc;
+    hdfs_crc::HostPlan hp;
+    if (int rc = hdfs_crc::build_plan(pkts, npkts, &hp, absolute != 0))
+        return hdfs_crc::fail(rc, "invalid packet in batch");
+    const hdfs_crc::PlanTraits t = hdfs_crc::plan_traits(hp);
+    if (general_bits_out) *general_bits_out = t.general;
+    if (needs_z_out) *needs_z_out = t.needs_z ? 1 : 0;
+    return 0;
+}
 
 extern "C" int crc32c_debug_plan(const crc32c_packet *pkts, size_t npkts, void *tiles, size_t tiles_cap, void *gen,
                                  size_t gen_cap, uint64_t *ntiles, uint64_t *ngen) {

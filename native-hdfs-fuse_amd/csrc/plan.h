@@ -168,4 +168,29 @@ int build_write_plan(const crc32c_buffer *buffers, uint32_t n_buffers, uint64_t 
 // (the lowest address read, rounded down to 16; 0 when nothing is read).
 void rebase_plan(HostPlan *plan, uint64_t *base);
 
+// What a plan's work items decide about its launches: which build runs them
+// (plan_select.h select_plan_build reads `general`) and how much of the
+// lookup image that build stages.  Computed once per plan (plan_traits).
+struct PlanTraits {
+    // KParams::general (plan_select.h kGeneral*) of a launch whose payload
+    // base, and every block's, is 16-byte aligned; launch_general adds the rest.
+    uint32_t general = 0;
+    // Some item shifts block results by Z^(512 s): tiles of lg or M > 0,
+    // general tiles, the general / spanning items.  A batch of bpc-512 tiles
+    // only (configs 2, 3, 4) stages the image without its Z section: 80 of 88
+    // KiB (split image), 20 of 28 KiB (compact).
+    bool needs_z = false;
+    bool gen_pow2 = true;  // every general tile's full chunks are 2^lg unpadded blocks (the resident kernel's)
+    // the resident queue's aligned-only build runs the plan: no GenItem, every
+    // tile a power-of-two tile 16-byte aligned from the block start
+    bool simple = true;
+};
+PlanTraits plan_traits(const HostPlan &hp);
+// KParams::general of a launch of the plan: the shifted loads also serve a
+// payload base, or a block of a multi-block launch, off 16-byte alignment.
+uint32_t launch_general(const PlanTraits &t, bool base_or_block_misaligned);
+
+// 0, or -EINVAL for a NULL packet array or a packet of bytesPerChecksum 0.
+int check_packets(const crc32c_packet *pkts, size_t npkts);
+
 }  // namespace hdfs_crc

@@ -88,13 +88,7 @@ struct DevicePlan {
     hipEvent_t uploaded = nullptr;
     std::atomic<bool> ready{false};  // the upload is known complete: launches need no wait
     uint32_t ntiles = 0, ngen = 0, nseg = 0, nconst = 0;
-    bool general = false;     // some tile is a general tile
-    bool misaligned = false;  // some power-of-two tile's offset is not a multiple of 16
-    bool padded = false;      // some general tile's full chunks are padded (bpc not 512 k)
-    bool half = false;        // some tile is a half tile (their own builds)
-    bool padtiles = false;    // some tile is a padded power-of-two tile (full-image general builds)
-    bool needs_z = true;      // some item shifts by Z^(512 s) (the image's last 7.5 KiB)
-    bool gen_pow2 = true;     // every general tile's full chunks are 2^lg unpadded blocks (the resident kernel's)
+    PlanTraits traits;  // plan_traits of the items (plan.h)
     size_t tiles_off = 0, gen_off = 0, seg_off = 0, pieces_off = 0, consts_off = 0, slots_off = 0;
 };
 
@@ -239,7 +233,7 @@ namespace hdfs_crc {
 // Kernel parameters of a plan's launch on (payload, out); checks nothing.
 KParams plan_params(const crc32c_plan *plan, const void *payload, uint32_t *out);
 // Uploads a HostPlan's items (and fresh verify slots) to the context's
-// device (into *dp), asynchronously; plan_ready orders a launch after it.
+// device (into *dp), asynchronously; prepare_launch orders a launch after it.
 int upload_plan(crc32c_ctx *ctx, const HostPlan &hp, DevicePlan *dp);
 // Before a launch of `plan` on `stream` (caller holds plan->mu): orders it
 // after the plan's upload and notes the stream for the plan's release

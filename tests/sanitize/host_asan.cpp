@@ -418,6 +418,138 @@ void zero_shifts(std::mt19937_64 &rng) {
     }
 }
 
+// plan_traits (plan.cpp: one pass, one classification per tile) against a
+// restatement in the other shape: one any-of loop over the tiles per fact,
+// the bits of KParams::general written as numbers.
+struct Facts {
+    uint32_t general;
+    bool needs_z, gen_pow2, simple;
+};
+
+Facts restate_traits(const hdfs_crc::HostPlan &hp) {
+    using hdfs_crc::FastTile;
+    using hdfs_crc::kGeneralTile;
+    using hdfs_crc::kHalfTile;
+    const uint32_t both = kGeneralTile | kHalfTile;
+    const auto any = [&](auto pred) { return std::any_of(hp.tiles.begin(), hp.tiles.end(), pred); };
+    const auto pad = [](const FastTile &t) { return (t.meta >> 18) & 511u; };
+    const char *e = std::getenv("HDFS_CRC32C_PADDED_FULL");
+    const bool padded_full = !(e && e[0] == '0');
+    const bool items = any([&](const FastTile &t) { return (t.meta & both) != 0 || pad(t) != 0; });
+    const bool half = any([&](const FastTile &t) { return (t.meta & both) == kHalfTile; });
+    const bool padded_tiles = any([&](const FastTile &t) { return !(t.meta & both) && pad(t) != 0; });
+    const bool misaligned = any([&](const FastTile &t) { return !(t.meta & both) && !pad(t) && (t.src & 15u); });
+    const bool padded_chunks = any([&](const FastTile &t) { return !(t.meta & kHalfTile) && pad(t) != 0; });
+    const bool z_tile = any([&](const FastTile &t) { return (t.meta & kGeneralTile) || ((t.meta >> 8) & 0xffu); });
+    const bool odd_general = any([&](const FastTile &t) {
+        const uint32_t k = (t.meta >> 8) & 31u;
+        return (t.meta & both) == kGeneralTile && (pad(t) != 0 || k == 0 || (k & (k - 1u)) != 0);
+    });
+    Facts f;
+    f.general = (items ? 1u : 0u) | ((misaligned || (!half && padded_chunks && padded_full)) ? 2u : 0u) |
+                (half ? 4u : 0u) | (padded_tiles ? 8u : 0u);
+    f.needs_z = !hp.gen.empty() || !hp.seg.empty() || z_tile;
+    f.gen_pow2 = !odd_general;
+    f.simple = hp.gen.empty() && !misaligned && !items;
+    return f;
+}
+
+// times each of: the four general bits, needs_z, gen_pow2, simple was seen [false, true]
+uint64_t g_seen[7][2];
+
+void check_traits(const hdfs_crc::HostPlan &hp, const char *what, int it) {
+    const hdfs_crc::PlanTraits t = hdfs_crc::plan_traits(hp);
+    const Facts f = restate_traits(hp);
+    CHECK(t.general == f.general, "%s %d: general %x, restated %x", what, it, t.general, f.general);
+    CHECK(t.needs_z == f.needs_z, "%s %d: needs_z %d", what, it, int(t.needs_z));
+    CHECK(t.gen_pow2 == f.gen_pow2, "%s %d: gen_pow2 %d", what, it, int(t.gen_pow2));
+    CHECK(t.simple == f.simple, "%s %d: simple %d", what, it, int(t.simple));
+    CHECK(hdfs_crc::launch_general(t, false) == f.general && hdfs_crc::launch_general(t, true) == (f.general | 2u),
+          "%s %d: launch_general", what, it);
+    for (int b = 0; b < 4; ++b) g_seen[b][(f.general >> b) & 1u]++;
+    g_seen[4][f.needs_z]++;
+    g_seen[5][f.gen_pow2]++;
+    g_seen[6][f.simple]++;
+}
+
+void plan_traits_match() {
+    std::mt19937_64 rng(0x243F6A8885A308D3ull);
+    // 1. packet batches, relative and absolute (rebased, as a plan is made):
+    // every tile form and the item-only lengths, payload offsets 16-byte
+    // aligned and not, tails of 0, 1-3 (a GenItem) and >= 4 bytes
+    const uint32_t bpcs[] = {100, 256, 300, 512, 600, 700, 1000, 1024, 1100, 1536, 2000, 4096, 8192, 9000};
+    for (int it = 0; it < 600; ++it) {
+        const bool absolute = it % 2 != 0;
+        std::vector<crc32c_packet> pk(1 + rng() % 4);
+        const bool same = rng() % 2 != 0, aligned = rng() % 2 != 0;  // (one bpc / every packet aligned: the pure cases)
+        const uint32_t bpc0 = bpcs[rng() % 14];
+        uint64_t off = (rng() % 4 == 0 ? 0 : 4096 * (1 + rng() % 8) + 16 * (rng() % 256)), out = 0;
+        if (absolute) off += 0x7f0000000000ull;
+        for (auto &p : pk) {
+            p.bpc = same ? bpc0 : bpcs[rng() % 14];
+            const uint32_t tails[] = {0u, uint32_t(1 + rng() % 3), uint32_t(4 + rng() % (p.bpc - 4))};
+            p.len = uint32_t((same && aligned ? 16 : 1 + rng() % 40) * p.bpc + tails[same && aligned ? 0 : rng() % 3]);
+            p.payload_off = off + (aligned ? 0 : 1 + rng() % 15);
+            p.out_idx = out;
+            out += crc32c_nchunks(p.len, p.bpc);
+            off = (p.payload_off + p.len + 15) & ~uint64_t(15);
+        }
+        hdfs_crc::HostPlan hp;
+        CHECK(hdfs_crc::build_plan(pk.data(), pk.size(), &hp, absolute) == 0, "traits: plan rc");
+        uint64_t base = 0;
+        if (absolute) hdfs_crc::rebase_plan(&hp, &base);
+        check_traits(hp, absolute ? "absolute batch" : "relative batch", it);
+    }
+    // 2. write plans over buffer lists with zero-fill buffers (addresses only:
+    // nothing is read through them)
+    uint64_t with_seg = 0, with_consts = 0, two_piece = 0;
+    for (int it = 0; it < 300; ++it) {
+        std::vector<crc32c_buffer> bufs(2 + rng() % 4);
+        uint64_t addr = 0x7f0000000000ull + 4096 * (rng() % 64), total = 0;
+        for (size_t i = 0; i < bufs.size(); ++i) {
+            bufs[i].len = rng() % 4 == 0 ? rng() % 50 : 1 + rng() % 90000;
+            addr += rng() % 2 ? 0 : 1 + rng() % 15;
+            bufs[i].data = (it + i) % 3 == 1 ? nullptr : reinterpret_cast<const void *>(uintptr_t(addr));
+            addr = (addr + bufs[i].len + 4095) & ~uint64_t(4095);
+            total += bufs[i].len;
+        }
+        const uint32_t wbpcs[] = {512, 1024, 100, 1000, 1536, 4096};
+        const uint32_t bpc = wbpcs[rng() % 6];
+        const uint64_t boff = rng() % 2 ? 0 : rng() % (total / 4 + 1);
+        hdfs_crc::HostPlan hp;
+        CHECK(hdfs_crc::build_write_plan(bufs.data(), uint32_t(bufs.size()), boff, total - boff, rng() % 2 ? 0 : rng() % 100000,
+                                         rng() % 2 ? 65536u : bpc * uint32_t(1 + rng() % 8), bpc, hdfs_crc::kPoly,
+                                         &hp) == 0,
+              "traits: write plan rc");
+        uint64_t base = 0;
+        hdfs_crc::rebase_plan(&hp, &base);
+        with_seg += !hp.seg.empty();
+        with_consts += !hp.consts.empty();
+        for (const auto &s : hp.seg) two_piece += s.npieces >= 2;  // (a chunk with bytes in two data buffers)
+        check_traits(hp, "write plan", it);
+    }
+    CHECK(with_seg && with_consts && two_piece, "write plans: %llu with SegItems, %llu with ConstRuns, %llu chunks in two buffers",
+          (unsigned long long)with_seg, (unsigned long long)with_consts, (unsigned long long)two_piece);
+    // 3. the empty plan, and tiles no builder makes: both form bits set
+    hdfs_crc::HostPlan hp;
+    check_traits(hp, "empty plan", 0);
+    const hdfs_crc::PlanTraits none = hdfs_crc::plan_traits(hp);
+    CHECK(none.general == 0 && !none.needs_z && none.gen_pow2 && none.simple, "empty plan traits");
+    for (uint32_t meta : {0xC0000001u, 0xC0000001u | (3u << 8) | (5u << 18)})
+        for (uint64_t src : {16ull, 21ull}) {
+            hp.tiles.push_back(hdfs_crc::FastTile{src, 0u, meta});
+            check_traits(hp, "both form bits", int(hp.tiles.size()));
+        }
+    const char *names[7] = {"kGeneralItems", "kGeneralShift", "kGeneralHalf", "kGeneralPadded", "needs_z", "gen_pow2", "simple"};
+    for (int k = 0; k < 7; ++k) {
+        std::printf("plan_traits %-14s false %llu true %llu\n", names[k], (unsigned long long)g_seen[k][0],
+                    (unsigned long long)g_seen[k][1]);
+        CHECK(g_seen[k][0] && g_seen[k][1], "plan_traits: %s never seen %s", names[k], g_seen[k][0] ? "true" : "false");
+    }
+    std::printf("plan_traits write plans: %llu with SegItems, %llu with ConstRuns, %llu chunks in two data buffers\n",
+                (unsigned long long)with_seg, (unsigned long long)with_consts, (unsigned long long)two_piece);
+}
+
 }  // namespace
 
 int main() {
@@ -429,6 +561,7 @@ int main() {
     frames_parse(rng);
     table_images();
     zero_shifts(rng);
+    plan_traits_match();
     if (g_fail) {
         std::fprintf(stderr, "%d failures\n", g_fail);
         return 1;

@@ -805,8 +805,8 @@ def _z_cases():
 @pytest.mark.parametrize("name,pk,z", list(_z_cases()), ids=[c[0] for c in _z_cases()])
 @pytest.mark.parametrize("absolute", [False, True], ids=["relative", "absolute"])
 def test_needs_z_and_general_bits_match_the_items(hdfs, name, pk, z, absolute):
-    """needs_z and the predicates behind KParams::general (static in
-    crc32c_runtime.hip, through crc32c_debug_packets_flags) against a reading
+    """needs_z and the bits of KParams::general (plan_traits in plan.cpp,
+    through crc32c_debug_packets_flags) against a reading
     of the plan's items written here: Z is needed iff there is a gen item, a
     general tile, a half tile with M > 0, or a power-of-two / padded tile with
     lg > 0."""

@@ -30,6 +30,9 @@ def test_host_sources_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "host sanitizer run clean" in r.stdout
+    # (plan_traits against its restatement: every fact seen both ways, the counts shown with -s)
+    print("".join(line + "\n" for line in r.stdout.splitlines() if line.startswith("plan_traits ")))
+    assert r.stdout.count("plan_traits ") == 8
 
 
 TSAN = ["-fsanitize=thread", "-fno-omit-frame-pointer", "-g", "-O1"]
