@@ -118,6 +118,29 @@ typedef struct crc32c_debug_launch_info {
 int crc32c_debug_plan_launch_info(const crc32c_plan *plan, const void *dev_payload, int verify,
                                   crc32c_debug_launch_info *out);
 
+/* The launches crc32c_plan_exec_blocks (verify != 0: the verify launches of
+ * crc32c_plan_verify_blocks, before its verdict launch) would make over
+ * these blocks, in order: the blocks first_block .. first_block + nblocks - 1
+ * of each, what it would hand the kernel -- ntiles over all its blocks, the
+ * `general` bits (a block off 16-byte alignment included), skip_z -- the CU
+ * count it is sized for and the build chosen from them by the same selector.
+ * per_block = 1: the plan has items other than tiles, so it has no
+ * multi-block form and the call makes one ordinary launch per block (one
+ * entry each; a verify call of such a plan is refused, here as there).  The
+ * entry walks the launch path's own grouping and parameter code.  Launches
+ * nothing and reads no device memory.  dev_outs only enters an exec call's
+ * grouping (outputs of one launch lie within 2^32 checksums); NULL: block
+ * k's checksums at index k * nchecksums of one array.  Fills at most cap
+ * entries of out and returns the number of launches, or -EINVAL for what the
+ * call itself refuses of plan, payloads and outputs. */
+typedef struct crc32c_debug_blocks_launch {
+    uint32_t first_block, nblocks, ntiles, general, skip_z, num_cu, per_block, reserved;
+    crc32c_debug_build build;
+} crc32c_debug_blocks_launch;
+int crc32c_debug_plan_blocks_launch_info(const crc32c_plan *plan, const void *const *dev_payloads,
+                                         uint32_t *const *dev_outs, size_t nblocks, int verify,
+                                         crc32c_debug_blocks_launch *out, size_t cap);
+
 /* The launch-path predicates over the work items of a packet batch
  * (absolute != 0: payload offsets are device addresses): *general_bits as a
  * plan of these packets on a 16-byte aligned payload would set them, and

@@ -73,6 +73,13 @@ class DebugLaunchInfo(ctypes.Structure):
                 ("num_cu", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("build", DebugBuild)]
 
 
+class DebugBlocksLaunch(ctypes.Structure):
+    """crc32c_debug_blocks_launch: one launch of a multi-block call and the build chosen for it."""
+    _fields_ = [("first_block", ctypes.c_uint32), ("nblocks", ctypes.c_uint32), ("ntiles", ctypes.c_uint32),
+                ("general", ctypes.c_uint32), ("skip_z", ctypes.c_uint32), ("num_cu", ctypes.c_uint32),
+                ("per_block", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("build", DebugBuild)]
+
+
 class DebugAesLaunch(ctypes.Structure):
     """crc32c_debug_aes_launch: the sizing of one AES/CTR launch."""
     _fields_ = [("windows", ctypes.c_uint64), ("wave_units", ctypes.c_uint64),
@@ -311,6 +318,7 @@ def _bind(L):
         "crc32c_verify_frames_host": (i32, [vp, vp, sz, u32, u64, u32, ctypes.POINTER(FramesResult)]),
         "crc32c_debug_select_build": (i32, [u32, u32, u32, u32, u32, i32, u32, ctypes.POINTER(DebugBuild)]),
         "crc32c_debug_plan_launch_info": (i32, [vp, vp, i32, ctypes.POINTER(DebugLaunchInfo)]),
+        "crc32c_debug_plan_blocks_launch_info": (i32, [vp, vp, vp, sz, i32, vp, sz]),
         "crc32c_debug_packets_flags": (i32, [vp, sz, i32, ctypes.POINTER(u32), ctypes.POINTER(i32)]),
         "hdfs_aes_ctr_init": (i32, [vp, vp, u32, vp]),
         "hdfs_aes_ctr_counter": (None, [vp, u64, vp]),
@@ -1055,6 +1063,21 @@ class Plan:
         _check(lib().crc32c_debug_plan_launch_info(self.handle, ctypes.c_void_p(dev_payload), int(verify),
                                                    ctypes.byref(info)), "crc32c_debug_plan_launch_info")
         return info
+
+    def blocks_launch_info(self, dev_payloads, dev_outs=None, verify: bool = False) -> list:
+        """crc32c_debug_plan_blocks_launch_info: a DebugBlocksLaunch for every launch exec_blocks (verify:
+        the verify launches of verify_blocks) would make over these blocks; launches nothing."""
+        n = len(dev_payloads)
+        pays = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_payloads])
+        outs = None
+        if dev_outs is not None:
+            assert len(dev_outs) == n
+            outs = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(x) for x in dev_outs])
+        info = (DebugBlocksLaunch * max(n, 1))()  # (never more launches than blocks)
+        rc = lib().crc32c_debug_plan_blocks_launch_info(self.handle, pays, outs, n, int(verify), info, max(n, 1))
+        if rc < 0:
+            _check(rc, "crc32c_debug_plan_blocks_launch_info")
+        return list(info[:rc])
 
     def close(self) -> None:
         if self.handle:

@@ -1269,27 +1269,38 @@ static KParams blocks_params(const crc32c_plan *plan, const void *const *dev_pay
     return p;
 }
 
-int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs, size_t nblocks,
-                hipStream_t s, hipEvent_t stop) {
+// What crc32c_plan_exec_blocks refuses before it launches anything.
+static int exec_blocks_check(const crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs,
+                             size_t nblocks) {
     if (!plan) return fail(-EINVAL, "plan == NULL");
     if (plan->absolute) return fail(-EINVAL, "a multi-block launch takes a plan of one block's shape, not device addresses");
     if (nblocks && (!dev_payloads || !dev_outs)) return fail(-EINVAL, "payloads/outs == NULL");
-    if (plan->nchecksums == 0 || nblocks == 0) {
-        if (stop) HIP_TRY(hipEventRecord(stop, s));
-        return 0;
-    }
+    if (plan->nchecksums == 0) return 0;
     for (size_t i = 0; i < nblocks; ++i)
         if ((!dev_payloads[i] && plan_reads_payload(plan)) || !dev_outs[i] || (uintptr_t(dev_outs[i]) & 3u))
             return fail(-EINVAL, "block %zu: payload NULL, or out NULL / not 4-byte aligned", i);
-    DeviceGuard guard(plan->ctx->device);
+    return 0;
+}
+
+// A plan with items other than tiles -- tails under 4 bytes, bpc outside
+// [4, 8192] -- has no multi-block form.
+static bool blocks_per_block(const crc32c_plan *plan) {
     const DevicePlan &dp = plan->dp;
-    if (dp.ngen || dp.nseg || dp.nconst || dp.ntiles == 0) {
-        // (items other than tiles -- tails under 4 bytes, bpc outside [4, 8192]
-        // -- have no multi-block form: one launch per block)
+    return dp.ngen || dp.nseg || dp.nconst || dp.ntiles == 0;
+}
+
+// The launches of crc32c_plan_exec_blocks over checked arguments, in order:
+// each(i, j, p, per_block) for blocks i .. j - 1 with kernel parameters p;
+// per_block: the plan has no multi-block form and every block takes one
+// ordinary launch.  Stops at the first each() that returns non-zero.  The
+// launch path and crc32c_debug_plan_blocks_launch_info both walk this.
+template <typename Each>
+static int each_exec_blocks_launch(const crc32c_plan *plan, const void *const *dev_payloads,
+                                   uint32_t *const *dev_outs, size_t nblocks, Each each) {
+    const DevicePlan &dp = plan->dp;
+    if (blocks_per_block(plan)) {
         for (size_t i = 0; i < nblocks; ++i)
-            if (int rc = launch_plan(plan, plan_params(plan, dev_payloads[i], dev_outs[i]), s,
-                                     i + 1 == nblocks ? stop : nullptr))
-                return rc;
+            if (int rc = each(i, i + 1, plan_params(plan, dev_payloads[i], dev_outs[i]), true)) return rc;
         return 0;
     }
     const uint64_t max_launch_tiles = UINT32_MAX;
@@ -1311,8 +1322,67 @@ int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *co
         const KParams p = blocks_params(plan, dev_payloads, i, j, reinterpret_cast<uint32_t *>(olo), [&](size_t k) {
             return uint32_t((uintptr_t(dev_outs[k]) - olo) / 4);
         });
-        if (int rc = launch_plan(plan, p, s, j == nblocks ? stop : nullptr)) return rc;
+        if (int rc = each(i, j, p, false)) return rc;
         i = j;
+    }
+    return 0;
+}
+
+int exec_blocks(crc32c_plan *plan, const void *const *dev_payloads, uint32_t *const *dev_outs, size_t nblocks,
+                hipStream_t s, hipEvent_t stop) {
+    if (int rc = exec_blocks_check(plan, dev_payloads, dev_outs, nblocks)) return rc;
+    if (plan->nchecksums == 0 || nblocks == 0) {
+        if (stop) HIP_TRY(hipEventRecord(stop, s));
+        return 0;
+    }
+    DeviceGuard guard(plan->ctx->device);
+    return each_exec_blocks_launch(plan, dev_payloads, dev_outs, nblocks,
+                                   [&](size_t, size_t j, const KParams &p, bool) {
+                                       return launch_plan(plan, p, s, j == nblocks ? stop : nullptr);
+                                   });
+}
+
+// What crc32c_plan_verify_blocks refuses of plan and payloads before it
+// launches anything (n = plan->nchecksums != 0, nblocks != 0).
+static int verify_blocks_check(const crc32c_plan *plan, const void *const *dev_payloads, size_t nblocks) {
+    const uint64_t n = plan->nchecksums;
+    if (blocks_per_block(plan))
+        return fail(-EINVAL, "a plan with items other than tiles (a short packet tail, a packet under one chunk, bpc "
+                             "outside [4, 8192]) has no multi-block verify: use crc32c_plan_verify_bitmap per block");
+    // (a launch's bitmap indices and tile count stay below 2^32)
+    if (n > (1ull << 27) || uint64_t(kMaxLaunchBlocks) * plan->dp.ntiles > UINT32_MAX)
+        return fail(-EINVAL, "a block of %llu checksums is more than a multi-block verify holds (2^27)",
+                    (unsigned long long)n);
+    if (!dev_payloads) return fail(-EINVAL, "payloads == NULL");
+    // Launch g: blocks 32 g .. 32 g + 31, payload deltas from the lowest
+    // (16-byte aligned) address among them, below 2^47 (tile offsets keep a
+    // tail length in bits 48-63).
+    for (size_t i = 0; i < nblocks; i += kMaxLaunchBlocks) {
+        uintptr_t plo = UINTPTR_MAX, phi = 0;
+        for (size_t k = i; k < std::min<size_t>(nblocks, i + kMaxLaunchBlocks); ++k) {
+            if (!dev_payloads[k]) return fail(-EINVAL, "block %zu: payload NULL", k);
+            const uintptr_t pp = uintptr_t(dev_payloads[k]) & ~uintptr_t(15);
+            plo = std::min(plo, pp), phi = std::max(phi, pp);
+        }
+        if (phi - plo >= (uintptr_t(1) << 47))
+            return fail(-EINVAL, "blocks %zu..: payloads more than 2^47 bytes apart in one launch", i);
+    }
+    return 0;
+}
+
+// The verify launches of crc32c_plan_verify_blocks over checked arguments, in
+// order: each(i, j, p) for launch i / kMaxLaunchBlocks over blocks i .. j - 1;
+// p is without the launch's expected values, result and bitmap.  (out_delta:
+// expected values and bitmap bits of the launch's block k - i.)
+template <typename Each>
+static int each_verify_blocks_launch(const crc32c_plan *plan, const void *const *dev_payloads, size_t nblocks,
+                                     Each each) {
+    const uint64_t n = plan->nchecksums;
+    for (size_t i = 0; i < nblocks; i += kMaxLaunchBlocks) {
+        const size_t j = std::min<size_t>(nblocks, i + kMaxLaunchBlocks);
+        if (int rc = each(i, j, blocks_params(plan, dev_payloads, i, j, nullptr,
+                                              [&](size_t k) { return uint32_t((k - i) * n); })))
+            return rc;
     }
     return 0;
 }
@@ -1345,47 +1415,26 @@ int crc32c_plan_verify_blocks(crc32c_plan *plan, const void *const *dev_payloads
         return fail(-EINVAL, "a multi-block verify takes a plan of one block's shape, not device addresses or buffers");
     const uint64_t n = plan->nchecksums;
     if (n == 0 || nblocks == 0) return 0;
-    const DevicePlan &dp = plan->dp;
-    if (dp.ngen || dp.nseg || dp.nconst || dp.ntiles == 0)
-        return fail(-EINVAL, "a plan with items other than tiles (a short packet tail, a packet under one chunk, bpc "
-                             "outside [4, 8192]) has no multi-block verify: use crc32c_plan_verify_bitmap per block");
-    // (a launch's bitmap indices and tile count stay below 2^32)
-    if (n > (1ull << 27) || uint64_t(kMaxLaunchBlocks) * dp.ntiles > UINT32_MAX)
-        return fail(-EINVAL, "a block of %llu checksums is more than a multi-block verify holds (2^27)",
-                    (unsigned long long)n);
-    if (!dev_payloads || !dev_expected || !dev_verdicts || !dev_work)
-        return fail(-EINVAL, "payloads/expected/verdicts/work == NULL");
+    // (all checked before the first launch)
+    if (int rc = verify_blocks_check(plan, dev_payloads, nblocks)) return rc;
+    if (!dev_expected || !dev_verdicts || !dev_work) return fail(-EINVAL, "expected/verdicts/work == NULL");
     if ((uintptr_t(dev_expected) | uintptr_t(dev_verdicts) | uintptr_t(dev_work)) & 3u)
         return fail(-EINVAL, "expected/verdicts/work not 4-byte aligned");
-    // Launch g: blocks 32 g .. 32 g + 31, payload deltas from the lowest
-    // (16-byte aligned) address among them, below 2^47 (tile offsets keep a
-    // tail length in bits 48-63).  All checked before the first launch.
-    for (size_t i = 0; i < nblocks; i += kMaxLaunchBlocks) {
-        uintptr_t plo = UINTPTR_MAX, phi = 0;
-        for (size_t k = i; k < std::min<size_t>(nblocks, i + kMaxLaunchBlocks); ++k) {
-            if (!dev_payloads[k]) return fail(-EINVAL, "block %zu: payload NULL", k);
-            const uintptr_t pp = uintptr_t(dev_payloads[k]) & ~uintptr_t(15);
-            plo = std::min(plo, pp), phi = std::max(phi, pp);
-        }
-        if (phi - plo >= (uintptr_t(1) << 47))
-            return fail(-EINVAL, "blocks %zu..: payloads more than 2^47 bytes apart in one launch", i);
-    }
     DeviceGuard guard(plan->ctx->device);
     const hipStream_t s = static_cast<hipStream_t>(stream);
     uint32_t *bitmap = static_cast<uint32_t *>(dev_work);
     uint32_t *results = bitmap + verify_blocks_bitmap_words(plan, nblocks);
-    for (size_t i = 0, g = 0; i < nblocks; i += kMaxLaunchBlocks, ++g) {
-        const size_t j = std::min<size_t>(nblocks, i + kMaxLaunchBlocks);
-        // (out_delta: expected values and bitmap bits of the launch's block k - i)
-        KParams p = blocks_params(plan, dev_payloads, i, j, nullptr, [&](size_t k) { return uint32_t((k - i) * n); });
-        // 32 n bits are whole words: launch g's bitmap starts at word g n and
-        // its own clear (verify_init) covers exactly its words
-        p.expect = dev_expected + uint64_t(i) * n;
-        p.result = results + 2 * g;
-        p.bad_bits = bitmap + g * n;
-        p.bad_words = uint32_t((uint64_t(j - i) * n + 31) / 32);
-        if (int rc = launch_plan(plan, p, s)) return rc;
-    }
+    if (int rc = each_verify_blocks_launch(plan, dev_payloads, nblocks, [&](size_t i, size_t j, KParams p) {
+            // 32 n bits are whole words: launch g's bitmap starts at word g n and
+            // its own clear (verify_init) covers exactly its words
+            const size_t g = i / kMaxLaunchBlocks;
+            p.expect = dev_expected + uint64_t(i) * n;
+            p.result = results + 2 * g;
+            p.bad_bits = bitmap + g * n;
+            p.bad_words = uint32_t((uint64_t(j - i) * n + 31) / 32);
+            return launch_plan(plan, p, s);
+        }))
+        return rc;
     return launch_verdicts(plan->ctx, bitmap, uint64_t(nblocks) * n, uint32_t(n), dev_verdicts, results,
                            kMaxLaunchBlocks, s);
 }
@@ -1504,6 +1553,49 @@ int crc32c_debug_plan_launch_info(const crc32c_plan *plan, const void *dev_paylo
     out->num_cu = uint32_t(plan->ctx->num_cu);
     put_build(select_plan_build(p.ntiles, p.ngen, p.nseg, p.nconst, p.general, verify != 0, out->num_cu), &out->build);
     return 0;
+}
+
+int crc32c_debug_plan_blocks_launch_info(const crc32c_plan *plan, const void *const *dev_payloads,
+                                         uint32_t *const *dev_outs, size_t nblocks, int verify,
+                                         crc32c_debug_blocks_launch *out, size_t cap) {
+    if (!plan || (cap && !out)) return fail(-EINVAL, "plan/out == NULL");
+    if (plan->absolute) return fail(-EINVAL, "a multi-block call takes a plan of one block's shape, not device addresses");
+    if (plan->nchecksums == 0 || nblocks == 0) return 0;
+    size_t count = 0;
+    auto put = [&](size_t i, size_t j, const KParams &p, bool per_block) {
+        if (count < cap) {
+            crc32c_debug_blocks_launch &o = out[count];
+            std::memset(&o, 0, sizeof o);
+            o.first_block = uint32_t(i);
+            o.nblocks = uint32_t(j - i);
+            o.ntiles = p.ntiles;
+            o.general = p.general;
+            o.skip_z = p.skip_z;
+            o.num_cu = uint32_t(plan->ctx->num_cu);
+            o.per_block = per_block ? 1u : 0u;
+            put_build(select_plan_build(p.ntiles, p.ngen, p.nseg, p.nconst, p.general, verify != 0, o.num_cu), &o.build);
+        }
+        ++count;
+        return 0;
+    };
+    if (verify) {
+        if (int rc = verify_blocks_check(plan, dev_payloads, nblocks)) return rc;
+        each_verify_blocks_launch(plan, dev_payloads, nblocks,
+                                  [&](size_t i, size_t j, const KParams &p) { return put(i, j, p, false); });
+    } else {
+        // (no outputs given: block k's checksums at index k * nchecksums of one array)
+        std::vector<uint32_t *> outs;
+        if (!dev_outs && dev_payloads) {
+            outs.resize(nblocks);
+            for (size_t k = 0; k < nblocks; ++k)
+                outs[k] = reinterpret_cast<uint32_t *>(uintptr_t(4096) + 4 * uint64_t(k) * plan->nchecksums);
+            dev_outs = outs.data();
+        }
+        if (int rc = exec_blocks_check(plan, dev_payloads, dev_outs, nblocks)) return rc;
+        each_exec_blocks_launch(plan, dev_payloads, dev_outs, nblocks, put);
+    }
+    if (count > size_t(INT32_MAX)) return fail(-EINVAL, "%zu launches are more than the return value holds", count);
+    return int(count);
 }
 
 int crc32c_chunks_dev(crc32c_ctx *ctx, const crc32c_packet *pkts, size_t npkts, const void *dev_payload,

@@ -1101,7 +1101,13 @@ def test_padded_power_of_two_tiles(hdfs, gpu_ctx, orc, npk):
 @pytest.mark.parametrize("bpc", [1000, 4000, 300])
 def test_padded_tiles_multi_block_launch(hdfs, gpu_ctx, orc, bpc):
     """crc32c_plan_exec_blocks with a one-block plan of padded tiles over
-    blocks at 16-byte-aligned and odd device addresses."""
+    blocks at 16-byte-aligned and odd device addresses -- through the
+    per-block fallback: the block starts at payload offset 0, and a padded (or
+    half) chunk within 16 bytes of the payload start is a gen item (so is every
+    packet's tail at bpc 4000 and 1100), so the plan has no multi-block form
+    and exec_blocks makes one ordinary launch per block.  The report must say
+    so.  (Padded and half tiles INSIDE a multi-block launch:
+    test_gpu_multi_block.py.)"""
     torch = _torch()
     pk = oracle.uniform_packets(64)
     pk["bpc"] = bpc
@@ -1119,7 +1125,11 @@ def test_padded_tiles_multi_block_launch(hdfs, gpu_ctx, orc, bpc):
     outs = torch.zeros((3, n), dtype=torch.int32, device="cuda")
     plan = hdfs.Plan(gpu_ctx, pk)
     stream = torch.cuda.current_stream()
-    plan.exec_blocks([dev.data_ptr() + o for o in offs], [outs[b].data_ptr() for b in range(3)], stream.cuda_stream)
+    pays, optrs = [dev.data_ptr() + o for o in offs], [outs[b].data_ptr() for b in range(3)]
+    report = plan.blocks_launch_info(pays, optrs)
+    assert [(r.first_block, r.nblocks, r.per_block) for r in report] == [(0, 1, 1), (1, 1, 1), (2, 1, 1)]
+    assert report[2].general & 2  # (the odd address: that block's own launch shifts its loads)
+    plan.exec_blocks(pays, optrs, stream.cuda_stream)
     stream.synchronize()
     plan.close()
     got = outs.cpu().numpy().view(np.uint32)
@@ -1183,5 +1193,7 @@ def test_half_tiles(hdfs, gpu_ctx, orc, npk):
 @pytest.mark.parametrize("bpc", [700, 100, 768, 256, 1100])
 def test_half_tiles_multi_block_launch(hdfs, gpu_ctx, orc, bpc):
     """crc32c_plan_exec_blocks with a one-block plan of half tiles over blocks
-    at 16-byte-aligned and odd device addresses."""
+    at 16-byte-aligned and odd device addresses: as above, the per-block
+    fallback (the first chunk of the block is a gen item), asserted there
+    through the report."""
     test_padded_tiles_multi_block_launch(hdfs, gpu_ctx, orc, bpc)

@@ -922,7 +922,9 @@ def test_last_plan_of_a_closed_context_destroyed_during_a_capture(hdfs, orc):
 def _block_shape(kind):
     if kind == "full":  # one 4 MiB block of 64 x 64 KiB packets
         return oracle.uniform_packets(64)
-    if kind == "ragged":  # a short block: 15 packets + a 1000-byte tail packet (general tile)
+    if kind == "ragged":  # a short block: 15 packets + a 1000-byte tail packet, whose 488-byte last chunk is
+        # a gen item (a tail of at most one 512-byte block behind bpc-512 chunks), not a tile: like
+        # "tiny_tail", no multi-block form, one launch per block
         pk = oracle.uniform_packets(16)
         pk["len"][-1] = 1000
         return pk
@@ -939,8 +941,11 @@ def _block_shape(kind):
 def test_plan_exec_blocks(hdfs, gpu_ctx, orc, kind):
     """crc32c_plan_exec_blocks: one block's plan run over 40 blocks in
     separate device buffers (some off 16-byte alignment, outputs in separate
-    arrays and inside one shared array) -- two launches of <= 32 blocks --
-    every block bit-exact against the oracle."""
+    arrays and inside one shared array) -- two launches of <= 32 blocks for
+    the tiles-only shapes ("full", "bpc1536"), the per-block fallback of 40
+    ordinary launches for the shapes with a gen item ("ragged", "tiny_tail"),
+    as the launch report must say -- every block bit-exact against the
+    oracle."""
     torch = _torch()
     pk = _block_shape(kind)
     n = oracle.total_checksums(pk)
@@ -962,7 +967,17 @@ def test_plan_exec_blocks(hdfs, gpu_ctx, orc, kind):
             outs.append((shared, (b // 2) * n))
     plan = gpu_ctx.plan(pk)
     stream = torch.cuda.current_stream()
-    plan.exec_blocks(pays, [o.data_ptr() + 4 * off for o, off in outs], stream.cuda_stream)
+    optrs = [o.data_ptr() + 4 * off for o, off in outs]
+    report = plan.blocks_launch_info(pays, optrs)
+    if kind in ("ragged", "tiny_tail"):
+        assert [(r.first_block, r.nblocks, r.per_block) for r in report] == [(b, 1, 1) for b in range(40)]
+    else:
+        # (32 + 8 blocks unless the allocator spread the buffers past one launch's reach)
+        assert not any(r.per_block for r in report) and report[0].nblocks > 1
+        assert all(r.nblocks <= 32 and r.ntiles == r.nblocks * report[0].ntiles // report[0].nblocks for r in report)
+        assert [r.first_block for r in report] == list(np.cumsum([0] + [r.nblocks for r in report[:-1]]))
+        assert sum(r.nblocks for r in report) == 40
+    plan.exec_blocks(pays, optrs, stream.cuda_stream)
     torch.cuda.synchronize()
     for b, (o, off) in enumerate(outs):
         got = o.cpu().numpy().view(np.uint32)[off:off + n]
